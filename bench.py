@@ -24,6 +24,12 @@ decode time.  Such a dispatch costs the step ~8 us, hence the sampling.
 --timing markers brackets the launches with hipEventRecord instead (each record
 adds ~2-4 us to the bracketed kernel's time).
 
+A plain run (--gpus/--steps/--warmup) does only what the headline needs: set
+up, warm up, time the steps, print the line.  Everything else -- the roofline's
+extra kernel-timed steps, the round-trip check, every optional section and the
+CPU baselines -- runs with --full.  --dump-outputs DIR writes what the last
+timed step computed (see dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -55,6 +61,12 @@ def parse(argv=None):
                     help="ranks, one per GPU (default: WORLD_SIZE under a launcher, else 1)")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the roofline's extra "
+                         "kernel-timed steps, the round-trip check, the optional sections (all of them, "
+                         "or those --sections / --no-* leave) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0) to DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="time budget of the CPU baseline sample (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -75,7 +87,7 @@ def parse(argv=None):
                          "step ~8 us; timing every step cost 7-9%% of throughput)")
     ap.add_argument("--roofline-samples", type=int, default=30,
                     help="extra encode/decode steps after the timed region whose kernels carry "
-                         "events, added to the roofline's kernel-time sample")
+                         "events, added to the roofline's kernel-time sample (--full only)")
     ap.add_argument("--no-fused", action="store_true",
                     help="skip the fused Golay read (shim_read_batch) measurement")
     ap.add_argument("--no-rows", action="store_true",
@@ -97,13 +109,16 @@ def parse(argv=None):
                     help="weak (default): every rank owns a whole [8,4096,32,128] tensor; strong: the ONE "
                          "[8,4096,32,128] tensor is split along B over the ranks (at most 8)")
     ap.add_argument("--no-sections", action="store_true",
-                    help="headline only: skip every optional section and the CPU baselines")
+                    help="with --full: skip every optional section and the CPU baselines")
     ap.add_argument("--sections", default=None,
-                    help="comma-separated sections to run, every other one skipped: " + ",".join(SECTIONS))
+                    help="with --full: comma-separated sections to run, every other one skipped: "
+                         + ",".join(SECTIONS))
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"))
     ap.add_argument("--inject-pmc-json", default=os.path.join(REPO, "profiles", "inject_valu.json"),
                     help="VALU instructions per Philox (rocprofv3 SQ_INSTS_VALU pass) for the inject roofline")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.no_sections and a.sections is None:
         a.sections = ""
     if a.sections is not None:
@@ -427,6 +442,43 @@ class Headline:
     def step(self, st=None):
         self.ops.golay_encode_into(self.trip.view(-1), self.cw, self.m)
         self.ops.golay_decode_into(self.noisy, self.out_trip, self.counts, self.stats if st is None else st)
+
+
+DUMP_SAMPLE = 1 << 20  # codewords written by --dump-outputs (32 MiB of .npy in all)
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, hl, stats):
+    """What the timed step hands its caller, after its last run: golay_encode's
+    codewords, golay_decode's triplets and per-codeword counts, and the decode
+    statistics accumulated over the timed steps.  The per-codeword arrays are a
+    fixed sample (DUMP_SEED) of DUMP_SAMPLE codeword indices, ascending, or all of
+    them when there are fewer; every integer is exact in the type it is stored in.
+
+      sample_index.npy   float64 [n]     codeword indices of the rows below
+      codewords.npy      float64 [n]     golay_encode output (int32)
+      triplets.npy       float32 [n, 3]  golay_decode of the BER-1e-2 codewords (uint8)
+      error_counts.npy   float32 [n]     golay_decode's count per codeword (uint8)
+      decode_stats.npy   float64 [2]     bits_corrected, uncorrectable over the timed steps
+    """
+    import numpy as np
+    m = hl.m
+    if m <= DUMP_SAMPLE:
+        idx = torch.arange(m, dtype=torch.int64)
+    else:
+        gen = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, m, (DUMP_SAMPLE,), generator=gen, dtype=torch.int64).sort().values
+    didx = idx.to(hl.cw.device)
+    arrays = {
+        "sample_index": idx.to(torch.float64),
+        "codewords": hl.cw[didx].to(torch.float64),
+        "triplets": hl.out_trip.view(-1, 3)[didx].to(torch.float32),
+        "error_counts": hl.counts[didx].to(torch.float32),
+        "decode_stats": hl.ops.stats_totals(stats).to(torch.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def fused_decode_bench(dev, steps, warmup, packed=False):
@@ -758,8 +810,16 @@ def main(argv=None):
     t1 = time.perf_counter()
 
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hl, stats)
+    full = args.full  # everything below that the headline does not need
+    if not full:
+        if args.sections and rank == 0:
+            print("bench: --sections has no effect without --full", file=sys.stderr)
+        for flag in SECTIONS.values():
+            setattr(args, flag, True)
     timed = [events[k] for k in sampled]
-    if kernel_timing and args.roofline_samples > 0:
+    if full and kernel_timing and args.roofline_samples > 0:
         # more kernel-carried samples for the roofline, after the timed region
         # (the throughput above is untouched; statistics go to a scratch buffer)
         scratch = ops.new_stats(dev)
@@ -790,7 +850,7 @@ def main(argv=None):
 
     # ---- correctness spot check (outside timing) -----------------------------
     ref_trip, ref_stats = None, None
-    if rank == 0:
+    if full and rank == 0:
         chk = ops.new_stats(dev)
         ops.golay_decode_into(cw, out_trip, counts, chk)  # clean codewords round-trip
         torch.cuda.synchronize()
@@ -1001,6 +1061,8 @@ def main(argv=None):
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
+        "full": full,
+        "outputs_dumped": args.dump_outputs,
         "scaling": args.scaling,
         "vs_baseline": None,
         "dtype": "u8/int32 (bitwise)",
@@ -1029,7 +1091,7 @@ def main(argv=None):
                      "kernel": "golay_decode_kernel", "bytes_per_launch": DECODE_BYTES_PER_CW * m,
                      "timing": (f"HIP events carried by the kernel dispatches (hipExtLaunchKernel) "
                                 f"of every {args.event_every}th timed step and of "
-                                f"{args.roofline_samples} steps after the timed region "
+                                f"{len(timed) - len(sampled)} steps after the timed region "
                                 f"({len(timed)} samples)" if kernel_timing else
                                 f"hipEventRecord markers on every {args.event_every}th timed step")},
         "decode_stats": {"bits_corrected": bits, "uncorrectable": unc, "steps": args.steps},

@@ -30,8 +30,8 @@ def _json_line(stdout):
 @pytest.mark.gpu
 def test_bench_spawns_two_gloo_ranks(gpu):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-inject", "--no-packed",
-                        "--no-fused", "--no-rows", "--roofline-samples", "2", "--no-sections"],
+                        "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-inject",
+                        "--no-packed", "--no-fused", "--no-rows", "--roofline-samples", "2", "--no-sections"],
                        capture_output=True, text=True, timeout=240, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -55,8 +55,8 @@ def test_bench_rccl_world1(gpu):
     per-rank all_gather and the statistics all_reduce) on a real "nccl" group of
     one rank -- what every rank of the driver's 8-GPU run executes."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--dist",
-                        "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-inject", "--no-packed",
-                        "--no-fused", "--no-rows", "--roofline-samples", "2", "--no-sections"],
+                        "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-inject",
+                        "--no-packed", "--no-fused", "--no-rows", "--roofline-samples", "2", "--no-sections"],
                        capture_output=True, text=True, timeout=240, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -113,7 +113,8 @@ def test_bench_sharded_sweep_and_strong_scaling_equal_one_rank(gpu):
     scaling split of the headline tensor.  Two gloo ranks sharing cuda:0 must
     give the single rank's counter table (same sha256) and the same all-reduced
     decode / injection statistics."""
-    common = ["--steps", "3", "--warmup", "1", "--roofline-samples", "1", "--sections", "montecarlo,strong"]
+    common = ["--full", "--steps", "3", "--warmup", "1", "--roofline-samples", "1",
+              "--sections", "montecarlo,strong"]
     one = _bench("--gpus", "1", *common)
     two = _bench("--gpus", "2", "--backend", "gloo", *common)
     m1, m2 = one["montecarlo"], two["montecarlo"]
@@ -134,7 +135,8 @@ def test_bench_sharded_sweep_and_strong_scaling_equal_one_rank(gpu):
 def test_bench_strong_headline_two_ranks(gpu):
     """--scaling strong: the headline itself splits the one tensor; value counts
     the whole tensor per step over the slowest rank, statistics equal one rank's."""
-    common = ["--steps", "4", "--warmup", "1", "--roofline-samples", "1", "--no-sections", "--scaling", "strong"]
+    common = ["--full", "--steps", "4", "--warmup", "1", "--roofline-samples", "1", "--no-sections",
+              "--scaling", "strong"]
     one = _bench("--gpus", "1", *common)
     two = _bench("--gpus", "2", "--backend", "gloo", *common)
     assert one["scaling"] == two["scaling"] == "strong"
@@ -153,7 +155,7 @@ def test_bench_under_torchrun_takes_the_launchers_world(gpu):
     port = launch.free_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-                        "--backend", "gloo", "--steps", "3", "--warmup", "1", "--roofline-samples", "1",
+                        "--backend", "gloo", "--full", "--steps", "3", "--warmup", "1", "--roofline-samples", "1",
                         "--sections", "montecarlo"],
                        capture_output=True, text=True, timeout=300, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
@@ -161,3 +163,44 @@ def test_bench_under_torchrun_takes_the_launchers_world(gpu):
     assert line["n_gpus"] == 2 and line["config"]["launcher"] == "external (torchrun)"
     assert line["config"]["process_group"] == {"backend": "gloo", "world_size": 2}
     assert line["montecarlo"]["world"] == 2 and len(line["montecarlo"]["per_rank"]) == 2
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(gpu, oracle, tmp_path):
+    """A plain run times --steps steps and nothing else (every --full figure is
+    absent); --dump-outputs writes the last step's arrays, at most 64 MB of
+    float32/float64 .npy, consistent with each other under the oracle."""
+    import numpy as np
+    out = tmp_path / "dump"
+    line = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out))
+    assert line["steps"] == 3 and line["full"] is False
+    assert line["ms_per_step"] == pytest.approx(
+        line["config"]["per_rank"][0]["elapsed_s"] / 3 * 1e3, rel=1e-9)
+    m = line["config"]["codewords_per_gpu"]
+    assert line["value"] == pytest.approx(m / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    for key in ("inject", "end_to_end_pipeline", "fused_golay_decode", "golay_rows", "interp", "fused_quant",
+                "strong_scaling", "montecarlo", "packed", "cpu_baseline", "cpu_backend"):
+        assert line[key] is None, key
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["codewords.npy", "decode_stats.npy", "error_counts.npy", "sample_index.npy", "triplets.npy"]
+    arr = {p.stem: np.load(p, allow_pickle=False) for p in out.iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 1000 * 1000
+    idx, cw = arr["sample_index"], arr["codewords"]
+    n = idx.size
+    assert n == 1 << 20 and cw.shape == (n,) and arr["triplets"].shape == (n, 3)
+    assert np.all(np.diff(idx) >= 0) and idx[0] >= 0 and idx[-1] < m
+    assert np.array_equal(cw, cw.astype(np.int32))
+    # the encode output is made of codewords: the oracle decodes it with nothing to correct
+    clean, cnt, (bits, unc) = oracle.golay_decode(cw.astype(np.int32))
+    assert bits == 0 and unc == 0 and not cnt.any()
+    # the decode of their BER-1e-2 corruption gives the same nibbles back except
+    # where 4 or more of the 24 bits flipped: P = sum_{k>=4} C(24,k) p^k (1-p)^(24-k)
+    # = 9.1e-5 at p = 1e-2, 95 of 2^20 expected (sigma 10); 200 is 10 sigma above
+    wrong = int((arr["triplets"] != clean).any(axis=1).sum())
+    print(f"rows differing from the clean nibbles: {wrong} of {n}")
+    assert 0 < wrong <= 200
+    # statistics over the 3 timed steps, each step the same decode
+    st = line["decode_stats"]
+    assert arr["decode_stats"].tolist() == [st["bits_corrected"], st["uncorrectable"]]
+    assert st["bits_corrected"] > 0 and st["bits_corrected"] % 3 == 0

@@ -144,6 +144,12 @@ def test_bench_sections_flag():
     assert a.gpus is None and not any(getattr(a, f) for f in bench.SECTIONS.values())
     with pytest.raises(SystemExit):
         bench.parse(["--sections", "nope"])
+    # the sections, the CPU baselines and the extra roofline steps run only with --full
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d" and (a.steps, a.warmup) == (7, 2)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
 
 
 def test_spawn_module_form(tmp_path):
