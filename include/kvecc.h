@@ -321,6 +321,33 @@ KVECC_API int kvecc_shim_write_strided(const void *k, const void *v, int64_t k_b
                                        float *k_scales, float *v_scales,
                                        const int32_t *block_table, int64_t num_layers,
                                        int64_t block_size, int64_t layer, void *stream);
+/* Append-mode write (no reference counterpart: the reference keeps one cache
+ * for the whole batch and never grows it): K and V [batch, q_len, hkv, d] by
+ * element strides as kvecc_shim_write_strided, quantized, encoded, injected
+ * and scattered in ONE launch for EVERY sequence of the batch.  block_table is
+ * [batch, table_stride] int32 (row b = sequence b); start_pos is a DEVICE
+ * int32 [batch] the host never reads.  Token t of sequence b goes to logical
+ * position p = start_pos[b] + t, physical block
+ * block_table[b*table_stride + p / block_size], slot p % block_size; caches and
+ * scales as kvecc_shim_write.  A row is skipped -- nothing written, nothing read
+ * past the table -- when start_pos[b] < 0 (inactive sequence), when
+ * p / block_size >= table_stride, or when the block id is negative.  Injection
+ * seeds are kvecc_shim_write's: K seed0 + r, V seed0 + r + 1 with the running
+ * row r = (b*q_len + t)*hkv + h, and skipped rows keep their r, so sequence b
+ * of an append at start_pos 0 holds the bits kvecc_shim_write stores for a
+ * batch of b + 1.  Same dtypes, codecs, scale_rule and n_bits clamps as
+ * kvecc_shim_write; d <= 512; table_stride >= 1; batch == 0 or q_len == 0
+ * enqueues nothing. */
+KVECC_API int kvecc_shim_append(const void *k, const void *v, int64_t k_batch_stride,
+                                int64_t k_seq_stride, int64_t k_head_stride,
+                                int64_t v_batch_stride, int64_t v_seq_stride,
+                                int64_t v_head_stride, int x_dtype, int64_t batch, int64_t q_len,
+                                int64_t hkv, int64_t d, int codec, int scale_rule, int n_bits,
+                                int inject, float ber, int64_t seed0, void *k_cache,
+                                void *v_cache, float *k_scales, float *v_scales,
+                                const int32_t *block_table, int64_t table_stride,
+                                const int32_t *start_pos, int64_t num_layers,
+                                int64_t block_size, int64_t layer, void *stream);
 /* ecc_shim.py:990-1071 (ECCBackend.attend, decode side) in ONE launch: gather
  * the first ctx tokens of layer `layer`, decode (H74: stats[0] += #flagged;
  * H84: stats[0] += #SINGLE_CORRECTED, stats[1] += #DOUBLE_DETECTED; Golay:
@@ -438,6 +465,15 @@ KVECC_API int kvecc_cpu_shim_write(const void *k, const void *v, int x_dtype, in
                                    void *v_cache, float *k_scales, float *v_scales,
                                    const int32_t *block_table, int64_t num_layers,
                                    int64_t block_size, int64_t layer, int threads);
+/* kvecc_shim_append on contiguous K/V [batch, q_len, hkv*d]; start_pos is a host int32 [batch] */
+KVECC_API int kvecc_cpu_shim_append(const void *k, const void *v, int x_dtype, int64_t batch,
+                                    int64_t q_len, int64_t hkv, int64_t d, int codec,
+                                    int scale_rule, int n_bits, int inject, float ber,
+                                    int64_t seed0, void *k_cache, void *v_cache, float *k_scales,
+                                    float *v_scales, const int32_t *block_table,
+                                    int64_t table_stride, const int32_t *start_pos,
+                                    int64_t num_layers, int64_t block_size, int64_t layer,
+                                    int threads);
 KVECC_API int kvecc_cpu_shim_read(const void *k_cache, const void *v_cache, const float *k_scales,
                                   const float *v_scales, const int32_t *block_table, int64_t ctx,
                                   int64_t hkv, int64_t d, int64_t num_layers, int64_t block_size,

@@ -597,6 +597,80 @@ KVECC_API int kvecc_cpu_decode_dequant_h84_rows(const uint8_t *cw, const float *
 
 // ---- shim write / read (host twins of shim.hip) ------------------------------
 
+// what a shim write needs to store one (side, row): shared by the overwrite
+// and the append twin
+struct HostShimRows {
+  const void *x[2];  // K, V: contiguous [rows, d]
+  void *cache[2];
+  float *scales[2];
+  int x_dtype, codec, scale_rule, n_bits, nb;
+  bool inj, golay, packed;
+  int64_t d, g;
+  uint32_t seed0, rowmul, thr;
+
+  int init(const char *fn, const void *k, const void *v, int x_dtype_, int64_t d_, int codec_, int scale_rule_,
+           int n_bits_, int inject, float ber, int64_t seed0_, void *k_cache, void *v_cache, float *k_scales,
+           float *v_scales, const int32_t *block_table, int64_t num_layers, int64_t block_size, int64_t layer) {
+    if (d_ < 1) return set_error(KVECC_EINVAL, "%s: empty rows", fn);
+    if (codec_ < KVECC_CODEC_NONE || codec_ > KVECC_CODEC_GOLAY_PACKED)
+      return set_error(KVECC_EINVAL, "%s: bad codec %d", fn, codec_);
+    if (scale_rule_ != KVECC_SCALE_DIV7 && scale_rule_ != KVECC_SCALE_MUL_INV7)
+      return set_error(KVECC_EINVAL, "%s: bad scale rule %d", fn, scale_rule_);
+    if (x_dtype_ < KVECC_F32 || x_dtype_ > KVECC_BF16) return set_error(KVECC_EINVAL, "%s: bad dtype %d", fn, x_dtype_);
+    if (num_layers < 1 || block_size < 1 || layer < 0 || layer >= num_layers)
+      return set_error(KVECC_EINVAL, "%s: bad cache geometry", fn);
+    if (!k || !v || !k_cache || !v_cache || !k_scales || !v_scales || !block_table)
+      return set_error(KVECC_EINVAL, "%s: null pointer", fn);
+    x[0] = k, x[1] = v;
+    cache[0] = k_cache, cache[1] = v_cache;
+    scales[0] = k_scales, scales[1] = v_scales;
+    x_dtype = x_dtype_, codec = codec_, scale_rule = scale_rule_, n_bits = n_bits_, d = d_;
+    packed = codec == KVECC_CODEC_GOLAY_PACKED;
+    golay = codec == KVECC_CODEC_GOLAY || packed;
+    g = golay ? (d + 2) / 3 : d;
+    seed0 = (uint32_t)(uint64_t)seed0_;
+    rowmul = (uint32_t)((uint64_t)g * (uint64_t)n_bits);
+    thr = kvecc_ber_threshold(ber);
+    inj = inject != 0 && ber > 0.0f;
+    nb = golay ? (n_bits < 0 ? 0 : (n_bits > 24 ? 24 : n_bits)) : (n_bits < 1 ? 1 : (n_bits > 8 ? 8 : n_bits));
+    return KVECC_OK;
+  }
+
+  // input row r of side `side` -> cache row `slot`; nib: 3 g + 3 scratch bytes
+  void store(int side, int64_t r, int64_t slot, std::vector<uint8_t> &nib) const {
+    const uint32_t key0 = (seed0 + (uint32_t)r + (uint32_t)side) * rowmul;
+    const void *xs = x[side];
+    float amax = 0.0f;
+    for (int64_t j = 0; j < d; ++j) amax = std::max(amax, std::fabs(load_x(xs, x_dtype, r * d + j)));
+    const float scale = row_scale(amax, scale_rule);
+    scales[side][slot] = scale;
+    if (!golay) {
+      uint8_t *c = reinterpret_cast<uint8_t *>(cache[side]) + slot * g;
+      for (int64_t j = 0; j < d; ++j) {
+        uint32_t cw = encode_nibble(quantize_nibble(load_x(xs, x_dtype, r * d + j), scale), codec);
+        if (inj) cw ^= philox_flip_mask<-1>(key0 + (uint32_t)j * (uint32_t)n_bits, (uint32_t)j, thr, nb);
+        c[j] = (uint8_t)cw;
+      }
+      return;
+    }
+    std::fill(nib.begin(), nib.end(), 0);
+    for (int64_t j = 0; j < d; ++j) nib[j] = (uint8_t)quantize_nibble(load_x(xs, x_dtype, r * d + j), scale);
+    for (int64_t q = 0; q < g; ++q) {
+      const uint32_t dw = golay_pack(nib[3 * q], nib[3 * q + 1], nib[3 * q + 2]);
+      uint32_t cw = dw | golay_parity12(dw) << 12;
+      if (inj) cw ^= philox_flip_mask<-1>(key0 + (uint32_t)q * (uint32_t)n_bits, (uint32_t)q, thr, nb);
+      if (packed) {
+        uint8_t *c = reinterpret_cast<uint8_t *>(cache[side]) + slot * KVECC_GOLAY_PACKED_ROW(g) + 3 * q;
+        c[0] = (uint8_t)cw;
+        c[1] = (uint8_t)(cw >> 8);
+        c[2] = (uint8_t)(cw >> 16);
+      } else {
+        reinterpret_cast<int32_t *>(cache[side])[slot * g + q] = (int32_t)cw;
+      }
+    }
+  }
+};
+
 KVECC_API int kvecc_cpu_shim_write(const void *k, const void *v, int x_dtype, int64_t batch,
                                    int64_t seq, int64_t hkv, int64_t d, int codec,
                                    int scale_rule, int n_bits, int inject, float ber,
@@ -606,67 +680,58 @@ KVECC_API int kvecc_cpu_shim_write(const void *k, const void *v, int x_dtype, in
                                    int64_t block_size, int64_t layer, int threads) {
   if (batch < 0 || seq < 0 || hkv < 0 || d < 0) return set_error(KVECC_EINVAL, "cpu_shim_write: negative size");
   if (batch == 0 || seq == 0 || hkv == 0) return KVECC_OK;
-  if (d < 1) return set_error(KVECC_EINVAL, "cpu_shim_write: empty rows");
-  if (codec < KVECC_CODEC_NONE || codec > KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL, "cpu_shim_write: bad codec %d", codec);
-  if (scale_rule != KVECC_SCALE_DIV7 && scale_rule != KVECC_SCALE_MUL_INV7)
-    return set_error(KVECC_EINVAL, "cpu_shim_write: bad scale rule %d", scale_rule);
-  if (x_dtype < KVECC_F32 || x_dtype > KVECC_BF16)
-    return set_error(KVECC_EINVAL, "cpu_shim_write: bad dtype %d", x_dtype);
-  if (num_layers < 1 || block_size < 1 || layer < 0 || layer >= num_layers)
-    return set_error(KVECC_EINVAL, "cpu_shim_write: bad cache geometry");
-  if (!k || !v || !k_cache || !v_cache || !k_scales || !v_scales || !block_table)
-    return set_error(KVECC_EINVAL, "cpu_shim_write: null pointer");
-  const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
-  const bool golay = codec == KVECC_CODEC_GOLAY || packed;
-  const int64_t g = golay ? (d + 2) / 3 : d;
-  const uint32_t rowmul = (uint32_t)((uint64_t)g * (uint64_t)n_bits);
-  const uint32_t thr = kvecc_ber_threshold(ber);
-  const bool inj = inject != 0 && ber > 0.0f;
-  const int nb = golay ? (n_bits < 0 ? 0 : (n_bits > 24 ? 24 : n_bits))
-                       : (n_bits < 1 ? 1 : (n_bits > 8 ? 8 : n_bits));
+  HostShimRows rows;
+  const int rc = rows.init("cpu_shim_write", k, v, x_dtype, d, codec, scale_rule, n_bits, inject, ber, seed0, k_cache,
+                           v_cache, k_scales, v_scales, block_table, num_layers, block_size, layer);
+  if (rc != KVECC_OK) return rc;
   const int64_t per_side = seq * hkv;
   parallel_for(2 * per_side, threads, 1, [&](int64_t b, int64_t e, int) {
-    std::vector<uint8_t> nib(3 * g + 3);
+    std::vector<uint8_t> nib(3 * rows.g + 3);
     for (int64_t item = b; item < e; ++item) {
       const int side = (int)(item / per_side);
       const int64_t rr = item - side * per_side;
       const int64_t pos = rr / hkv, h = rr - pos * hkv;
-      const int64_t r = (batch - 1) * per_side + rr;
-      const uint32_t key0 = ((uint32_t)(uint64_t)seed0 + (uint32_t)r + (uint32_t)side) * rowmul;
+      const int64_t r = (batch - 1) * per_side + rr;  // only the last batch is stored
       const int64_t slot =
           (((int64_t)block_table[pos / block_size] * num_layers + layer) * hkv + h) * block_size +
           pos % block_size;
-      const void *x = side ? v : k;
-      float amax = 0.0f;
-      for (int64_t j = 0; j < d; ++j) amax = std::max(amax, std::fabs(load_x(x, x_dtype, r * d + j)));
-      const float scale = row_scale(amax, scale_rule);
-      (side ? v_scales : k_scales)[slot] = scale;
-      if (!golay) {
-        uint8_t *c = reinterpret_cast<uint8_t *>(side ? v_cache : k_cache) + slot * g;
-        for (int64_t j = 0; j < d; ++j) {
-          uint32_t cw = encode_nibble(quantize_nibble(load_x(x, x_dtype, r * d + j), scale), codec);
-          if (inj) cw ^= philox_flip_mask<-1>(key0 + (uint32_t)j * (uint32_t)n_bits, (uint32_t)j, thr, nb);
-          c[j] = (uint8_t)cw;
-        }
-      } else {
-        std::fill(nib.begin(), nib.end(), 0);
-        for (int64_t j = 0; j < d; ++j) nib[j] = (uint8_t)quantize_nibble(load_x(x, x_dtype, r * d + j), scale);
-        void *cache = side ? v_cache : k_cache;
-        for (int64_t q = 0; q < g; ++q) {
-          const uint32_t dw = golay_pack(nib[3 * q], nib[3 * q + 1], nib[3 * q + 2]);
-          uint32_t cw = dw | golay_parity12(dw) << 12;
-          if (inj) cw ^= philox_flip_mask<-1>(key0 + (uint32_t)q * (uint32_t)n_bits, (uint32_t)q, thr, nb);
-          if (packed) {
-            uint8_t *c = reinterpret_cast<uint8_t *>(cache) + slot * KVECC_GOLAY_PACKED_ROW(g) + 3 * q;
-            c[0] = (uint8_t)cw;
-            c[1] = (uint8_t)(cw >> 8);
-            c[2] = (uint8_t)(cw >> 16);
-          } else {
-            reinterpret_cast<int32_t *>(cache)[slot * g + q] = (int32_t)cw;
-          }
-        }
-      }
+      rows.store(side, r, slot, nib);
+    }
+  });
+  return KVECC_OK;
+}
+
+// host twin of kvecc_shim_append: same placement, skip rules and seeds
+KVECC_API int kvecc_cpu_shim_append(const void *k, const void *v, int x_dtype, int64_t batch,
+                                    int64_t q_len, int64_t hkv, int64_t d, int codec,
+                                    int scale_rule, int n_bits, int inject, float ber,
+                                    int64_t seed0, void *k_cache, void *v_cache, float *k_scales,
+                                    float *v_scales, const int32_t *block_table,
+                                    int64_t table_stride, const int32_t *start_pos,
+                                    int64_t num_layers, int64_t block_size, int64_t layer,
+                                    int threads) {
+  if (batch < 0 || q_len < 0 || hkv < 0 || d < 0) return set_error(KVECC_EINVAL, "cpu_shim_append: negative size");
+  if (batch == 0 || q_len == 0 || hkv == 0) return KVECC_OK;
+  HostShimRows rows;
+  const int rc = rows.init("cpu_shim_append", k, v, x_dtype, d, codec, scale_rule, n_bits, inject, ber, seed0, k_cache,
+                           v_cache, k_scales, v_scales, block_table, num_layers, block_size, layer);
+  if (rc != KVECC_OK) return rc;
+  if (table_stride < 1) return set_error(KVECC_EINVAL, "cpu_shim_append: table stride %lld < 1", (long long)table_stride);
+  if (!start_pos) return set_error(KVECC_EINVAL, "cpu_shim_append: null pointer");
+  const int64_t per_side = batch * q_len * hkv;
+  parallel_for(2 * per_side, threads, 1, [&](int64_t b0, int64_t e0, int) {
+    std::vector<uint8_t> nib(3 * rows.g + 3);
+    for (int64_t item = b0; item < e0; ++item) {
+      const int side = (int)(item / per_side);
+      const int64_t r = item - side * per_side;  // (b * q_len + t) * hkv + h
+      const int64_t bt = r / hkv, h = r - bt * hkv;
+      const int64_t b = bt / q_len, t = bt - b * q_len;
+      if (start_pos[b] < 0) continue;
+      const int64_t p = (int64_t)start_pos[b] + t, lb = p / block_size;
+      if (lb >= table_stride) continue;
+      const int64_t blk = block_table[b * table_stride + lb];
+      if (blk < 0) continue;
+      rows.store(side, r, ((blk * num_layers + layer) * hkv + h) * block_size + p % block_size, nib);
     }
   });
   return KVECC_OK;

@@ -501,6 +501,24 @@ def shim_write_tensors(k, v, k_cache, v_cache, k_scales, v_scales, table, num_la
               _ptr(v_scales), _ptr(table), int(num_layers), int(block_size), int(layer), NUM_THREADS)
 
 
+def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
+                        block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
+    """Host twin of ops.shim_append_tensors (kvecc_cpu_shim_append): same
+    arguments, placement, skip rules and seeds; K/V are made contiguous."""
+    from .ops import _check_shim_append_args, _head_rows  # pure torch, device-agnostic
+    if k.device.type != "cpu":
+        raise ValueError(f"the cpu backend writes host tensors, k is on {k.device}")
+    batch, q_len = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
+                                           num_layers, block_size, hkv, d, layer, codec)
+    k4 = _head_rows(k, batch, q_len, hkv, d).contiguous()
+    v4 = _head_rows(v, batch, q_len, hkv, d).contiguous()
+    _lib.call("kvecc_cpu_shim_append", _ptr(k4), _ptr(v4), _DT[k.dtype], batch, q_len, int(hkv), int(d),
+              SHIM_CODECS[codec], _lib.scale_rule_code(scale_rule, DEFAULT_SCALE_RULE), int(n_bits),
+              int(bool(inject)), float(ber), int(seed0), _ptr(k_cache), _ptr(v_cache), _ptr(k_scales),
+              _ptr(v_scales), _ptr(block_table), block_table.shape[1], _ptr(start_pos), int(num_layers),
+              int(block_size), int(layer), NUM_THREADS)
+
+
 def shim_read(manager, layer, ctx, codec, interp, out_dtype, stats=None, seq_id=0):
     return shim_read_tensors(manager.k_cache, manager.v_cache, manager.k_scales, manager.v_scales,
                              manager.block_table[seq_id], ctx, manager.num_kv_heads, manager.head_dim,

@@ -98,13 +98,23 @@ class ECCShimConfig:
     int32 per codeword) or "packed" (3-byte codewords, token rows padded to 4
     bytes: 132 instead of 172 B per row at head_dim 128).  "packed" needs the
     fused write / read.
+    ``cache_mode`` is "overwrite" (the reference's behaviour and the default:
+    one cache for the whole batch, every forward writes from position 0) or
+    "append": batch row b is sequence b with its own blocks, and every forward
+    appends its tokens at the sequence's current length, so a patched model
+    generates token by token.  "append" needs a fused codec (int4, hamming74,
+    hamming84, golay) and fused=True.  ``decode_stats`` (append mode) sends
+    single-token steps through the counting read instead of the paged
+    attention kernels, which keep no statistics.
     """
 
     SUPPORTED_CODECS = {"fp16", "fp8", "int4", "hamming74", "hamming84", "golay"}
+    APPEND_CODECS = ("int4", "hamming74", "hamming84", "golay")
 
     def __init__(self, codec="hamming84", ber=0.0, block_size=16, num_blocks=256,
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
-                 fused=True, scale_rule=None, golay_storage="int32"):
+                 fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
+                 decode_stats=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -123,6 +133,13 @@ class ECCShimConfig:
         if golay_storage == "packed" and not fused:
             raise ValueError("golay_storage='packed' needs fused=True")
         self.golay_storage = golay_storage
+        if cache_mode not in ("overwrite", "append"):
+            raise ValueError(f"cache_mode must be 'overwrite' or 'append', not {cache_mode!r}")
+        if cache_mode == "append" and (codec not in self.APPEND_CODECS or not fused):
+            raise ValueError(f"cache_mode='append' needs fused=True and one of {self.APPEND_CODECS}, "
+                             f"not codec={codec!r}, fused={fused}")
+        self.cache_mode = cache_mode
+        self.decode_stats = decode_stats
 
 
 class SimpleBlockManager:
@@ -134,6 +151,10 @@ class SimpleBlockManager:
     golay_storage="packed" block_size * KVECC_GOLAY_PACKED_ROW(ceil(head_dim/3))
     uint8 (3-byte Golay codewords, not a reference layout);
     k_scales / v_scales: fp32 [num_blocks, num_layers, num_kv_heads, block_size].
+
+    Append mode (not in the reference) adds ctx_lens, int32 [num_layers,
+    max_seqs] on the device: how many tokens each layer holds of each sequence,
+    with extend / advance / free; callers that never append see no change.
     """
 
     def __init__(self, num_blocks, block_size, num_layers, num_kv_heads, head_dim, device="cuda",
@@ -179,6 +200,46 @@ class SimpleBlockManager:
         # a steady-state forward issues no host-to-device transfer and the
         # whole patched forward can be captured in a HIP graph
         self._block_ids = torch.arange(num_blocks, dtype=torch.int32, device=device)
+        # append mode: every layer's context length of every sequence, on the
+        # device (the append write's start_pos, the paged attention's
+        # context_lens) with a host mirror (allocation, max_context_len)
+        self.ctx_lens = torch.zeros((num_layers, self.max_seqs), dtype=torch.int32, device=device)
+        self._host_lens = [[0] * self.max_seqs for _ in range(num_layers)]
+
+    # ---- append mode: per-sequence, per-layer lengths ----------------------------
+    def layer_lens(self, layer, batch):
+        """Host mirror of ctx_lens[layer, :batch]."""
+        return self._host_lens[layer][:batch]
+
+    def advance(self, layer, batch, num_tokens):
+        """Layer `layer` of sequences [0, batch) grew by num_tokens (no host read)."""
+        self.ctx_lens[layer, :batch] += num_tokens
+        row = self._host_lens[layer]
+        for b in range(batch):
+            row[b] += num_tokens
+
+    def extend(self, seq_id, new_len):
+        """Blocks to cover new_len tokens of seq_id; the ones it has stay as they are."""
+        if new_len > self.seq_to_len.get(seq_id, 0):
+            self.allocate(seq_id, new_len)
+        return self.block_table[seq_id]
+
+    def free(self, seq_id):
+        """Return seq_id's blocks, zeroed: zero codewords decode clean, so a
+        re-used block adds no stale statistics."""
+        blocks = self.seq_to_blocks.pop(seq_id, [])
+        self.seq_to_len.pop(seq_id, None)
+        self._host_table.pop(seq_id, None)
+        if blocks:
+            idx = torch.tensor(blocks, dtype=torch.long, device=self.k_cache.device)
+            for t in (self.k_cache, self.v_cache, self.k_scales, self.v_scales):
+                t[idx] = 0
+            self.free_blocks.extend(blocks)
+            self.free_blocks.sort()
+        self.block_table[seq_id].fill_(-1)
+        self.ctx_lens[:, seq_id] = 0
+        for row in self._host_lens:
+            row[seq_id] = 0
 
     def allocate(self, seq_id, num_tokens):
         need = (num_tokens + self.block_size - 1) // self.block_size
@@ -219,6 +280,9 @@ class SimpleBlockManager:
         self.seq_to_len.clear()
         self._host_table.clear()
         self.block_table.fill_(-1)
+        self.ctx_lens.zero_()
+        for row in self._host_lens:
+            row[:] = [0] * self.max_seqs
         self.k_cache.zero_()
         self.v_cache.zero_()
         self.k_scales.zero_()
@@ -263,6 +327,10 @@ class ECCBackend:
         if manager.golay_packed and not self._fused_ok():
             raise ValueError("packed Golay storage needs the fused shim write / read "
                              "(fused=True, a backend with shim_write, head_dim <= 512)")
+        self.append = getattr(config, "cache_mode", "overwrite") == "append"
+        if self.append and not (self._fused_ok() and hasattr(self.codec_backend, "shim_append_tensors")):
+            raise ValueError("cache_mode='append' needs the fused shim kernels (fused=True, a backend with "
+                             "shim_append_tensors, head_dim <= 512 and a multiple of 4 for the byte codecs)")
         self.num_kv_groups = num_heads // self.num_kv_heads
         self._injection_count = 0
         self._total_values = 0
@@ -291,6 +359,8 @@ class ECCBackend:
     def write(self, k, v, layer_idx, seq_id=0):
         """Store K, V [batch, seq, kv_heads*head_dim] (or a [batch, seq, kv_heads,
         head_dim] view, which the fused path reads in place) for layer `layer_idx`."""
+        if self.append:
+            return self._append_write(k, v, layer_idx)
         cfg, mgr = self.config, self.manager
         batch, seq_len = k.shape[0], k.shape[1]
         d, hk = self.head_dim, self.num_kv_heads
@@ -349,6 +419,78 @@ class ECCBackend:
         if inject:
             self._injection_count += rows
 
+    # ---- append mode (no reference counterpart) -----------------------------------
+    def check_append_batch(self, batch):
+        if batch > self.manager.max_seqs:
+            raise ValueError(f"append mode holds {self.manager.max_seqs} sequences, got a batch of {batch}")
+
+    def _append_write(self, k, v, layer_idx):
+        """Batch row b is sequence b: its q_len tokens go behind the layer's
+        current length of that sequence, every sequence in one launch.  The
+        start positions are the manager's device lengths; nothing is read back."""
+        cfg, mgr = self.config, self.manager
+        batch, q_len = k.shape[0], k.shape[1]
+        self.check_append_batch(batch)
+        if k.dtype != v.dtype or k.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"append mode: K/V dtype {k.dtype}/{v.dtype} has no fused write")
+        d, hk = self.head_dim, self.num_kv_heads
+        self._total_values += 2 * batch * q_len * hk * d
+        for b, n in enumerate(mgr.layer_lens(layer_idx, batch)):
+            mgr.extend(b, n + q_len)
+        inject = cfg.inject_errors and cfg.ber > 0
+        seed0 = cfg.seed + self._injection_count
+        # the dispatcher operator while torch.compile traces, the C ABI otherwise
+        fn = torch.ops.kvecc.shim_append if self._traced() else self.codec_backend.shim_append_tensors
+        fn(k, v, mgr.k_cache, mgr.v_cache, mgr.k_scales, mgr.v_scales, mgr.block_table[:batch],
+           mgr.ctx_lens[layer_idx, :batch], mgr.num_layers, mgr.block_size, hk, d, layer_idx, mgr.shim_codec,
+           _N_BITS[cfg.codec], inject, cfg.ber, seed0, cfg.scale_rule)
+        mgr.advance(layer_idx, batch, q_len)
+        if inject:
+            self._injection_count += batch * q_len * hk
+
+    def _append_attend(self, q, layer_idx):
+        """Attention of q [batch, heads, q_len, head_dim], row b over sequence
+        b's own cache; the layer's write has already advanced the lengths."""
+        cfg, mgr = self.config, self.manager
+        b, _, q_len, d = q.shape
+        lens = mgr.layer_lens(layer_idx, b)
+        ctx = max(lens)
+        if ctx == 0:
+            return torch.zeros_like(q)
+        table, dev_lens = mgr.block_table[:b], mgr.ctx_lens[layer_idx, :b]
+        interp = cfg.use_interpolation and cfg.codec == "hamming84"
+        if q_len == 1 and cfg.codec in ("hamming84", "golay") and not interp and not cfg.decode_stats \
+                and d <= 256:
+            # decode step: paged attention with inline decode over the ragged
+            # tables; no statistics, as on the reference's seq_len == 1 path
+            q1 = q[:, :, 0, :].contiguous()
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention(q1, mgr.k_cache, mgr.v_cache, table, dev_lens,
+                                                      mgr.k_scales, mgr.v_scales, layer_idx, mgr.block_size,
+                                                      1.0 / math.sqrt(d), mgr.shim_codec, ctx)
+                return out.unsqueeze(2)
+            out = torch.empty_like(q1)
+            self.codec_backend.paged_attention_into(
+                q1, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx)
+            return out.unsqueeze(2)
+        # prefill, chunks, hamming74 / int4, interpolation, decode_stats: one
+        # batched read at the longest length, then masked SDPA.  The read
+        # decodes ctx rows of every sequence: a shorter sequence's rows past
+        # its length are unwritten (zero codewords in a zeroed block, or no
+        # block at all), decode clean and add nothing to the statistics; the
+        # mask keeps them out of the attention.
+        k_t, v_t = self.codec_backend.shim_read_batch(
+            mgr.k_cache, mgr.v_cache, mgr.k_scales, mgr.v_scales, table, ctx, d, layer_idx, mgr.shim_codec,
+            q.dtype, stats=self._stats, interp=interp)
+        if self.num_kv_groups > 1:
+            k_t = k_t.repeat_interleave(self.num_kv_groups, dim=1)
+            v_t = v_t.repeat_interleave(self.num_kv_groups, dim=1)
+        # query t of sequence b sits at position start_b + t and sees keys j <= start_b + t
+        qpos = (dev_lens - q_len).view(b, 1, 1) + torch.arange(q_len, device=q.device).view(1, q_len, 1)
+        mask = torch.arange(ctx, device=q.device).view(1, 1, ctx) <= qpos
+        return F.scaled_dot_product_attention(q, k_t, v_t, attn_mask=mask.unsqueeze(1))
+
     def _traced(self):
         """True while torch.compile traces this backend and it is one whose
         kernels are registered as torch.ops.kvecc operators (hip, cpu): calls
@@ -396,6 +538,8 @@ class ECCBackend:
 
     def attend(self, q, layer_idx, seq_id=0):
         """Attention of q [batch, heads, seq, head_dim] over the decoded cache."""
+        if self.append:
+            return self._append_attend(q, layer_idx)
         cfg, mgr = self.config, self.manager
         ctx = mgr.get_context_len(seq_id)
         if ctx == 0:
@@ -557,7 +701,12 @@ class ECCPagedAttentionShim(nn.Module):
         q = self.q_proj(hidden_states).view(b, s, self.num_heads, self.head_dim).transpose(1, 2)
         k = self.k_proj(hidden_states).view(b, s, self.num_kv_heads, self.head_dim).transpose(1, 2)
         v = self.v_proj(hidden_states).view(b, s, self.num_kv_heads, self.head_dim).transpose(1, 2)
-        if position_ids is None:
+        if position_ids is None and self.backend.append:
+            # the tokens sit behind what this layer already holds of each sequence
+            self.backend.check_append_batch(b)
+            start = self.backend.manager.ctx_lens[self.layer_idx, :b].to(torch.long)
+            position_ids = start.unsqueeze(1) + torch.arange(s, device=hidden_states.device)
+        elif position_ids is None:
             position_ids = torch.arange(s, device=hidden_states.device).unsqueeze(0).expand(b, -1)
         cos, sin = self.rotary_emb(v, position_ids)
         q, k = self._apply_rotary_pos_emb(q, k, cos, sin)

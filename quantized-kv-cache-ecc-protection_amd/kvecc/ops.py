@@ -780,6 +780,74 @@ def _check_shim_read_args(k_cache, v_cache, k_scales, v_scales, block_table, ctx
     return batch, nl, hkv, bs
 
 
+def _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
+                            block_size, hkv, d, layer, codec):
+    """Validate an append write (both backends) before anything is written:
+    K/V dtype and shape, cache dtype and row geometry per codec, scales
+    [blocks, layers, hkv, block_size] fp32, block_table int32 [batch, n]
+    contiguous, start_pos int32 [batch], one device for every tensor.  A
+    mismatch raises ValueError.  Returns (batch, q_len)."""
+    if codec not in _SHIM_CACHE_DT:
+        raise ValueError(f"shim codec {codec!r} (int4, hamming74, hamming84, golay or golay_packed)")
+    if k.dtype not in _DT or v.dtype != k.dtype:
+        raise ValueError(f"K/V must share one of fp32/fp16/bf16, got {k.dtype}/{v.dtype}")
+    if k.dim() < 3 or k.shape != v.shape:
+        raise ValueError(f"K/V must share one [batch, q_len, ...] shape, got {tuple(k.shape)}/{tuple(v.shape)}")
+    batch, q_len = k.shape[0], k.shape[1]
+    if not 1 <= d <= 512 or hkv < 1 or k.numel() != batch * q_len * hkv * d:
+        raise ValueError(f"K/V {tuple(k.shape)} do not hold [batch, q_len, {hkv}, {d}] (head_dim in [1, 512])")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
+    nb = k_cache.shape[0]
+    for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if c.dtype != _SHIM_CACHE_DT[codec]:
+            raise ValueError(f"{codec} {name} must be {_SHIM_CACHE_DT[codec]}, got {c.dtype}")
+    per = {"golay": (d + 2) // 3, "golay_packed": (3 * ((d + 2) // 3) + 3) // 4 * 4}.get(codec, d)
+    if tuple(k_cache.shape[1:]) != (num_layers, hkv, block_size * per) or block_size < 1:
+        raise ValueError(f"{codec} caches must be [blocks, {num_layers}, {hkv}, {block_size}*{per}], got "
+                         f"{tuple(k_cache.shape)}")
+    if not 0 <= int(layer) < num_layers:
+        raise ValueError(f"layer {layer} outside the cache's {num_layers} layers")
+    for name, sc in (("k_scales", k_scales), ("v_scales", v_scales)):
+        if tuple(sc.shape) != (nb, num_layers, hkv, block_size) or sc.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 [{nb}, {num_layers}, {hkv}, {block_size}], got "
+                             f"{tuple(sc.shape)} {sc.dtype}")
+    if block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[0] != batch or \
+            block_table.shape[1] < 1:
+        raise ValueError(f"block_table must be a contiguous int32 [{batch}, max_blocks] tensor")
+    if tuple(start_pos.shape) != (batch,) or start_pos.dtype != torch.int32:
+        raise ValueError(f"start_pos must be int32 [{batch}], got {start_pos.dtype} {tuple(start_pos.shape)}")
+    for name, t in (("v", v), ("k_cache", k_cache), ("v_cache", v_cache), ("k_scales", k_scales),
+                    ("v_scales", v_scales), ("block_table", block_table), ("start_pos", start_pos)):
+        if t.device != k.device:
+            raise ValueError(f"{name} is on {t.device}, k on {k.device}")
+        if name != "v" and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return batch, q_len
+
+
+def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
+                        block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
+    """Append-mode cache write (kvecc_shim_append): K, V [batch, q_len, hkv*d] or
+    [batch, q_len, hkv, d] (strided views read in place, as shim_write) ->
+    quantize, encode, per-row inject, scatter, one launch for every sequence.
+    Token t of sequence b lands at position start_pos[b] + t of block_table
+    row b; start_pos is a device int32 [batch] the host never reads.  Rows of a
+    sequence with start_pos < 0, past the table or in a -1 block are skipped."""
+    if not k.is_cuda:
+        raise ValueError(f"the hip backend writes GPU tensors, k is on {k.device}")
+    batch, q_len = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
+                                           num_layers, block_size, hkv, d, layer, codec)
+    k4 = _head_rows(k, batch, q_len, hkv, d)
+    v4 = _head_rows(v, batch, q_len, hkv, d)
+    _lib.call("kvecc_shim_append", _ptr(k4), _ptr(v4), k4.stride(0), k4.stride(1), k4.stride(2),
+              v4.stride(0), v4.stride(1), v4.stride(2), _DT[k.dtype], batch, q_len, int(hkv), int(d),
+              SHIM_CODECS[codec], _lib.scale_rule_code(scale_rule, DEFAULT_SCALE_RULE), int(n_bits),
+              int(bool(inject)), float(ber), int(seed0), _ptr(k_cache), _ptr(v_cache), _ptr(k_scales),
+              _ptr(v_scales), _ptr(block_table), block_table.shape[1], _ptr(start_pos), int(num_layers),
+              int(block_size), int(layer), _stream(k.device))
+
+
 def shim_read_batch(k_cache, v_cache, k_scales, v_scales, block_table, ctx, head_dim, layer, codec,
                     out_dtype, stats=None, interp=False, out=None):
     """The shim's fused read (gather -> decode -> dequantize, ecc_shim.py:990-1071)

@@ -287,6 +287,24 @@ def _(k, v, k_cache, v_cache, k_scales, v_scales, table, num_layers, block_size,
     return None
 
 
+@torch.library.custom_op("kvecc::shim_append", mutates_args=("k_cache", "v_cache", "k_scales", "v_scales"),
+                         device_types=_DEV)
+def shim_append(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, k_scales: Tensor, v_scales: Tensor,
+                block_table: Tensor, start_pos: Tensor, num_layers: int, block_size: int, hkv: int, d: int,
+                layer: int, codec: str, n_bits: int, inject: bool, ber: float, seed0: int,
+                scale_rule: Optional[str] = None) -> None:
+    """Append-mode cache write: token t of sequence b at start_pos[b] + t of
+    block_table row b (kvecc_shim_append; no reference counterpart)."""
+    _be(k).shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
+                               block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, scale_rule)
+
+
+@shim_append.register_fake
+def _(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers, block_size, hkv, d, layer,
+      codec, n_bits, inject, ber, seed0, scale_rule=None):
+    return None
+
+
 @torch.library.custom_op("kvecc::shim_read", mutates_args=("stats",), device_types=_DEV)
 def shim_read(k_cache: Tensor, v_cache: Tensor, k_scales: Tensor, v_scales: Tensor, table: Tensor, ctx: int,
               hkv: int, d: int, num_layers: int, block_size: int, layer: int, codec: str, interp: bool,
@@ -325,6 +343,6 @@ def _(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, la
 OPS: List[str] = ["hamming74_encode", "hamming84_encode", "hamming74_decode", "hamming84_decode",
                   "golay_encode", "golay_decode", "golay_encode_rows", "golay_decode_rows",
                   "inject_bit_errors", "inject_bit_errors_", "interpolate_double_errors",
-                  "fused_quantize_encode", "fused_decode_dequantize_hamming84", "shim_write", "shim_read",
-                  "paged_attention"]
+                  "fused_quantize_encode", "fused_decode_dequantize_hamming84", "shim_write", "shim_append",
+                  "shim_read", "paged_attention"]
 _ = _lib  # the operators bind libkvecc.so lazily, on first call

@@ -8,6 +8,7 @@ forward, as the reference's per-text loop does) next to the unpatched model,
 plus get_ecc_stats of one forward.  Prints one JSON line.
 
 usage: python tools/bench_shim.py [--codec hamming84] [--interp 1] [--bers 0 1e-3 1e-2]
+       python tools/bench_shim.py --append --steps 200 --warmup 20   (the append-mode write, append_bench)
 """
 
 from __future__ import annotations
@@ -133,8 +134,82 @@ def cpu_only(args):
     print(json.dumps(out))
 
 
+def append_bench(args):
+    """--append: the append-mode cache write (kvecc_shim_append) of one decode
+    step -- q_len 1, 8 KV heads, head_dim 128, fp16, batch 32 and batch 1 --
+    next to kvecc_shim_write at batch 1, seq 32, which has batch 32's row count
+    (2 * 32 * 8 waves).  Per case: kernel_us, the kernel's own duration
+    (kvecc_time_next_launch events, mean and min over --steps launches), and
+    call_us, events around --steps back-to-back wrapper calls (host argument
+    checks and launch included).  Writes the JSON to --out as well."""
+    from kvecc import ops
+    from kvecc.ecc_shim import SimpleBlockManager
+    dev = torch.device("cuda:0")
+    hkv, d, bs, layers, layer, at = 8, 128, 16, 2, 1, 100
+    steps, warmup = max(args.steps, 1), max(args.warmup, 1)
+
+    def measure(call):
+        for _ in range(warmup):
+            call()
+        evs = [ops.kernel_timer(dev) for _ in range(steps)]
+        torch.cuda.synchronize()
+        for e in evs:
+            ops.time_next_launch(*e)
+            call()
+        torch.cuda.synchronize()
+        ks = [e[0].elapsed_time(e[1]) * 1e3 for e in evs]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        return {"kernel_us": statistics.mean(ks), "kernel_us_min": min(ks), "call_us": e0.elapsed_time(e1) * 1e3 / steps}
+
+    out = {"config": {"kv_heads": hkv, "head_dim": d, "block_size": bs, "layers": layers, "layer": layer,
+                      "dtype": "fp16", "append_start_pos": at, "steps": steps, "warmup": warmup}, "runs": []}
+    g = torch.Generator().manual_seed(0)
+    for codec in ("hamming84", "golay", "golay_packed"):
+        n_bits = 8 if codec == "hamming84" else 24
+        for ber in (0.0, 1e-3):
+            def manager():
+                return SimpleBlockManager(32 * 8, bs, layers, hkv, d, device=dev, codec=codec.replace("_packed", ""),
+                                          golay_storage="packed" if codec == "golay_packed" else "int32")
+            for batch in (32, 1):
+                m = manager()
+                for b in range(batch):
+                    m.extend(b, at + 1)
+                m.ctx_lens[layer, :batch] = at
+                k = torch.randn(batch, 1, hkv, d, generator=g).half().to(dev)
+                v = torch.randn(batch, 1, hkv, d, generator=g).half().to(dev)
+                res = measure(lambda: ops.shim_append_tensors(
+                    k, v, m.k_cache, m.v_cache, m.k_scales, m.v_scales, m.block_table[:batch],
+                    m.ctx_lens[layer, :batch], layers, bs, hkv, d, layer, codec, n_bits, ber > 0, ber, 42))
+                out["runs"].append({"op": "shim_append", "codec": codec, "ber": ber, "batch": batch, "q_len": 1,
+                                    "rows": 2 * batch * hkv, **res})
+            m = manager()
+            m.allocate(0, 32)
+            k = torch.randn(1, 32, hkv, d, generator=g).half().to(dev)
+            v = torch.randn(1, 32, hkv, d, generator=g).half().to(dev)
+            res = measure(lambda: ops.shim_write_tensors(
+                k, v, m.k_cache, m.v_cache, m.k_scales, m.v_scales, m.block_table[0], layers, bs, hkv, d, layer,
+                codec, n_bits, ber > 0, ber, 42))
+            out["runs"].append({"op": "shim_write", "codec": codec, "ber": ber, "batch": 1, "seq": 32,
+                                "rows": 2 * 32 * hkv, **res})
+    text = json.dumps(out, indent=1)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--append", action="store_true",
+                    help="time the append-mode cache write of a decode step against the equal-row shim_write")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "append", "append_write.json"),
+                    help="where --append also writes its JSON ('' for stdout only)")
     ap.add_argument("--codec", default="hamming84")
     ap.add_argument("--interp", type=int, default=1)
     ap.add_argument("--golay-storage", default="int32", choices=["int32", "packed"])
@@ -157,6 +232,8 @@ def main():
     from transformers import GPT2Config, GPT2LMHeadModel
     from kvecc.ecc_shim import (ECCShimConfig, get_ecc_stats, patch_model_with_ecc_attention,
                                 reset_ecc_cache)
+    if args.append:
+        return append_bench(args)
     if args.no_gpu:
         return cpu_only(args)
     dev = torch.device("cuda:0")
