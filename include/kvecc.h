@@ -381,8 +381,10 @@ KVECC_API int kvecc_shim_read_batch(const void *k_cache, const void *v_cache, co
  * token per sequence, query [batch, heads, head_dim] (q_dtype), caches as above
  * (codec H84: uint8, double errors keep their data; GOLAY: int32, uncorrectable
  * data kept; GOLAY_PACKED: 3-byte codewords, rows of KVECC_GOLAY_PACKED_ROW bytes), block_table [batch, max_blocks] int32 (-1 = no block, token
- * skipped), context_lens [batch] int32 (<= max_context_len; <= 0 means
- * max_blocks*block_size), out [batch, heads, head_dim] in q_dtype.  A sequence
+ * skipped), context_lens [batch] int32, max_context_len (<= 0 means
+ * max_blocks*block_size; a context_len above it, or above the table's
+ * max_blocks*block_size, is attended up to that bound, on the device and the
+ * host alike), out [batch, heads, head_dim] in q_dtype.  A sequence
  * with no valid token (context_len <= 0 or only -1 blocks) gets the reference's
  * values: -8.0 in every lane for H84 (its kernel's -1e20 masking,
  * attention_ecc.py:342,391-423), 0 for Golay (reference_attention_ecc).  Query head h reads cache head h / (heads / kv_heads).  `workspace`:

@@ -95,6 +95,7 @@ struct AttnArgs {
   int64_t heads, kv_heads, d, g;  // g = codewords per token row
   uint32_t rowb;                  // packed Golay: bytes per token row (KVECC_GOLAY_PACKED_ROW(g))
   int64_t layers, layer, bs, max_blocks, nsplit, split;
+  int64_t ctx_cap;  // min(max_context_len, max_blocks * bs): context_lens above it are attended up to it
   uint32_t cache_bytes, scale_bytes;  // buffer-load bounds (BUF kernels)
   float sm_scale;
   float empty_value;          // output when a (b, h) has no valid token
@@ -150,6 +151,8 @@ struct Chunk {
       }
     } else {
       const uint32_t off = ((uint32_t)row * (uint32_t)a.g + VEC * c) * 4u;
+      // g % 3 != 0: the row's last lane reads past the row, at the cache's last row past the
+      // descriptor's range, which is checked per dword (pinned by tests/test_attention_paths.py)
       if constexpr (VEC == 3) {  // one 12-byte load: 71.9 vs 72.6 us per MHA call against
                                  // three dword loads (profiles/r06/attn/golay_no_gather_probe.txt)
         const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, off, 0, 0);
@@ -507,7 +510,7 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_kernel(AttnArgs a) {
   const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;  // query heads h0 .. h0+G-1
   const int64_t hk = h0 / (a.heads / a.kv_heads);
   const int grp = threadIdx.x / W, c = threadIdx.x % W;
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.max_blocks * a.bs);  // table bound
+  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);  // max_context_len and the table
   const int64_t t0 = (int64_t)blockIdx.x * a.split;
   const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
@@ -861,7 +864,7 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_kernel(AttnArgs
   const int64_t hgroups = a.heads / G;
   const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;
   const int64_t hk = h0 / (a.heads / a.kv_heads);
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.max_blocks * a.bs);
+  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);
   const int64_t t0 = (int64_t)blockIdx.x * a.split;
   const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
@@ -1113,7 +1116,7 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_kernel(AttnAr
   const int64_t hgroups = a.heads / G;
   const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;
   const int64_t hk = h0 / (a.heads / a.kv_heads);
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.max_blocks * a.bs);
+  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);
   const int64_t t0 = (int64_t)blockIdx.x * a.split;
   const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
@@ -1631,6 +1634,7 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
   a.layer = layer;
   a.bs = block_size;
   a.max_blocks = max_blocks;
+  a.ctx_cap = std::min(max_context_len, max_blocks * block_size);
   a.sm_scale = sm_scale;
   a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
   int gq = 1, gm = 0;

@@ -257,3 +257,99 @@ def test_reused_blocks_add_no_stale_statistics_cpu():
         reset_ecc_cache(model)
         fresh, _ = short_run()
     assert reused == fresh and fresh["errors_corrected"] > 0
+
+
+# ---- 9. ragged generation ---------------------------------------------------------------------------------
+# Batch 2: a 7-token prefill, free(1), a 3-token chunk (masked SDPA, layer lengths 10 / 3), then
+# two single-token steps (the paged path, 11 / 4 and 12 / 5).  Row 1 starts a new sequence at
+# position 0 in the freed row, with its own tokens and position_ids.
+RAG_PRE, RAG_CHUNK, RAG_STEPS = 7, 3, 2
+RAG_LENS = [RAG_PRE + RAG_CHUNK + RAG_STEPS, RAG_CHUNK + RAG_STEPS]
+
+
+def _ragged_ids():
+    g = torch.Generator().manual_seed(17)
+    return [torch.randint(0, 101, (n,), generator=g) for n in (RAG_LENS[0], RAG_PRE, RAG_LENS[1])]
+
+
+def _forwards(model, ids, starts, sizes):
+    """One forward per size over ids [B, sum(sizes)], row b starting at position starts[b] -> logits."""
+    outs, at = [], 0
+    for n in sizes:
+        pos = torch.stack([s + at + torch.arange(n) for s in starts]).to(ids.device)
+        outs.append(model(ids[:, at:at + n], position_ids=pos).logits.float())
+        at += n
+    return torch.cat(outs, dim=1)
+
+
+def _state(model, logits, lens):
+    from kvecc.ecc_shim import get_ecc_stats
+    mgr = model._ecc_block_manager
+    b = len(logits)
+    return dict(logits=[x.cpu() for x in logits], stats=get_ecc_stats(model),
+                lens=[mgr.layer_lens(layer, b) for layer in range(LAYERS)],
+                dev_lens=mgr.ctx_lens[:, :b].cpu().tolist(),
+                rows=[_layer0_rows(mgr, s, n) for s, n in enumerate(lens)])
+
+
+def _ragged_run(model, cfg, dev="cpu"):
+    from kvecc.ecc_shim import patch_model_with_ecc_attention, reset_ecc_cache
+    long, old, new = (t.to(dev) for t in _ragged_ids())
+    steps = [RAG_CHUNK] + [1] * RAG_STEPS
+    with torch.no_grad(), patch_model_with_ecc_attention(model, cfg, num_blocks=16):
+        reset_ecc_cache(model)
+        first = _forwards(model, torch.stack([long[:RAG_PRE], old]), [0, 0], [RAG_PRE])
+        model._ecc_block_manager.free(1)
+        rest = _forwards(model, torch.stack([long[RAG_PRE:], new]), [RAG_PRE, 0], steps)
+        return _state(model, [torch.cat([first[0], rest[0]]), rest[1]], RAG_LENS)
+
+
+def _alone_run(model, cfg, ids, sizes):
+    from kvecc.ecc_shim import patch_model_with_ecc_attention, reset_ecc_cache
+    with torch.no_grad(), patch_model_with_ecc_attention(model, cfg, num_blocks=16):
+        reset_ecc_cache(model)
+        return _state(model, [_forwards(model, ids[None], [0], sizes)[0]], [len(ids)])
+
+
+@pytest.mark.parametrize("codec", ["hamming84", "golay", "hamming74"])
+def test_ragged_rows_equal_the_sequences_alone_cpu(codec, exact_linear):
+    model, _ = _llama()
+    cfg = _cfg(codec, cache_mode="append")
+    long, _, new = _ragged_ids()
+    steps = [RAG_CHUNK] + [1] * RAG_STEPS
+    both = _ragged_run(model, cfg)
+    assert both["lens"] == [RAG_LENS] * LAYERS and both["dev_lens"] == [RAG_LENS] * LAYERS
+    for b, alone in enumerate((_alone_run(model, cfg, long, [RAG_PRE] + steps), _alone_run(model, cfg, new, steps))):
+        assert alone["lens"] == [[RAG_LENS[b]]] * LAYERS
+        for got, want in zip(both["rows"][b], alone["rows"][0]):
+            assert torch.equal(got, want), b
+        diff = (both["logits"][b] - alone["logits"][0]).abs().max().item()
+        print(f"ragged vs alone, {codec}, row {b}: max |diff| = {diff:.3e}")
+        assert torch.allclose(both["logits"][b], alone["logits"][0], atol=LOGIT_ATOL, rtol=LOGIT_ATOL), b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("codec", ["hamming84", "golay", "golay_packed"])
+def test_ragged_hip_equals_cpu_backend(gpu, codec):
+    model, _ = _llama()
+    cpu = _ragged_run(model, _cfg(codec, 1e-2, "cpu", cache_mode="append"))
+    hip = _ragged_run(model.to(gpu), _cfg(codec, 1e-2, "hip", cache_mode="append"), gpu)
+    assert hip["stats"] == cpu["stats"] and hip["stats"]["injection_count"] > 0
+    assert hip["lens"] == cpu["lens"] == [RAG_LENS] * LAYERS and hip["dev_lens"] == cpu["dev_lens"] == hip["lens"]
+    for b in range(2):
+        assert torch.allclose(hip["logits"][b], cpu["logits"][b], atol=LOGIT_ATOL, rtol=LOGIT_ATOL), b
+
+
+# ---- 10. head_dim 64: the decode steps take a GQA kernel (2 query heads per cache head) ---------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("codec", ["hamming84", "golay"])
+def test_hip_equals_cpu_backend_head_dim_64(gpu, codec):
+    model, _ = _llama(hidden_size=256)
+    assert model.config.hidden_size // model.config.num_attention_heads == 64
+    ids = _ids()
+    cpu = _run(model, ids, _cfg(codec, 1e-2, "cpu", cache_mode="append"))
+    model = model.to(gpu)
+    hip = _run(model, ids.to(gpu), _cfg(codec, 1e-2, "hip", cache_mode="append"))
+    assert hip["stats"] == cpu["stats"] and hip["lens"] == cpu["lens"] and hip["dev_lens"] == cpu["dev_lens"]
+    for t in range(TOTAL):
+        assert torch.allclose(hip["logits"][:, t].cpu(), cpu["logits"][:, t], atol=LOGIT_ATOL, rtol=LOGIT_ATOL), t

@@ -9,10 +9,11 @@ import torch
 LOGIT_ATOL = 2e-3
 
 
-def _llama():
+def _llama(hidden_size=128):
+    """head_dim = hidden_size / 4: 32, or 64 at hidden_size 256."""
     from transformers import LlamaConfig, LlamaForCausalLM
     torch.manual_seed(0)
-    cfg = LlamaConfig(vocab_size=101, hidden_size=128, intermediate_size=256, num_hidden_layers=2,
+    cfg = LlamaConfig(vocab_size=101, hidden_size=hidden_size, intermediate_size=256, num_hidden_layers=2,
                       num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=128)
     return LlamaForCausalLM(cfg).eval(), torch.randint(0, 101, (1, 20),
                                                        generator=torch.Generator().manual_seed(1))

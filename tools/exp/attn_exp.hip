@@ -74,6 +74,7 @@ __attribute__((visibility("default"))) int kvecc_exp_paged_attention_mfma(
   a.layer = layer;
   a.bs = block_size;
   a.max_blocks = max_blocks;
+  a.ctx_cap = std::min(max_context_len > 0 ? max_context_len : max_blocks * block_size, max_blocks * block_size);
   a.sm_scale = sm_scale;
   a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
   const int64_t rows_total = num_blocks * num_layers * kv_heads * block_size;
@@ -124,6 +125,7 @@ __attribute__((visibility("default"))) int kvecc_exp_paged_attention_packed(
   a.layer = 0;
   a.bs = block_size;
   a.max_blocks = max_blocks;
+  a.ctx_cap = std::min(max_context_len > 0 ? max_context_len : max_blocks * block_size, max_blocks * block_size);
   a.sm_scale = sm_scale;
   a.empty_value = 0.0f;
   const int64_t rows_total = num_blocks * kv_heads * block_size;
@@ -179,6 +181,7 @@ __attribute__((visibility("default"))) int kvecc_exp_paged_attention_gsp(
   a.layer = 0;
   a.bs = block_size;
   a.max_blocks = max_blocks;
+  a.ctx_cap = std::min(max_context_len > 0 ? max_context_len : max_blocks * block_size, max_blocks * block_size);
   a.sm_scale = sm_scale;
   a.empty_value = 0.0f;
   const int64_t rows_total = num_blocks * kv_heads * block_size;
