@@ -401,6 +401,36 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
                                     int codec, float *workspace, int64_t workspace_floats,
                                     void *stream);
 
+/* Chunked causal form: q_len query tokens per sequence (a prefill, a chunk of
+ * one, the draft tokens of a verify step) against the same caches, which
+ * already hold the chunk's own tokens: context_lens[b] counts them.  Query
+ * element (b, t, h, e) is query[b*q_batch_stride + t*q_token_stride +
+ * h*q_head_stride + e] (strides in elements, >= 0; head and token strides >=
+ * head_dim), so [batch, heads, q_len, d] and [batch, q_len, heads*d] tensors
+ * are both read in place; out is contiguous [batch, q_len, heads, head_dim] in
+ * q_dtype.  Query t of sequence b sits at position p = context_lens[b] - q_len
+ * + t and attends to the keys j with 0 <= j <= p and j < min(max_context_len,
+ * max_blocks*block_size); -1 blocks are skipped.  A row without a valid key
+ * (p < 0, or only -1 blocks at or before p) gets the decode entry's empty
+ * value, per row.  Codecs, dtypes, head_dim domain, GQA mapping and argument
+ * checks are kvecc_paged_attention's; q_len 1 with a contiguous query is that
+ * entry, bit for bit.  batch, q_len or heads 0 enqueue nothing; a shape beyond
+ * the grid limits is KVECC_EINVAL.  `workspace`:
+ * kvecc_paged_attention_chunk_workspace(...) floats (0 for an empty call,
+ * KVECC_EINVAL with a message for a negative size). */
+KVECC_API int64_t kvecc_paged_attention_chunk_workspace(int64_t batch, int64_t q_len, int64_t heads,
+                                                        int64_t head_dim, int64_t max_context_len);
+KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_stride,
+                                          int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                          const void *k_cache, const void *v_cache,
+                                          const int32_t *block_table, const int32_t *context_lens,
+                                          const float *k_scales, const float *v_scales, void *out,
+                                          int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
+                                          int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                          int64_t layer, int64_t block_size, int64_t max_blocks,
+                                          int64_t max_context_len, float sm_scale, int codec,
+                                          float *workspace, int64_t workspace_floats, void *stream);
+
 /* ---- Host ("cpu") backend ------------------------------------------------- */
 /* The reference has no CPU codec backend (every wrapper asserts x.is_cuda,
  * e.g. hamming74_triton.py:185,246, golay_triton.py:399,456); BASELINE config 1 asks
@@ -496,6 +526,15 @@ KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const vo
                                         int64_t num_blocks, int64_t num_layers, int64_t layer, int64_t block_size,
                                         int64_t max_blocks, int64_t max_context_len,
                                         float sm_scale, int codec, int threads);
+KVECC_API int kvecc_cpu_paged_attention_chunk(const void *query, int64_t q_batch_stride,
+                                              int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                              const void *k_cache, const void *v_cache,
+                                              const int32_t *block_table, const int32_t *context_lens,
+                                              const float *k_scales, const float *v_scales, void *out,
+                                              int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
+                                              int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                              int64_t layer, int64_t block_size, int64_t max_blocks,
+                                              int64_t max_context_len, float sm_scale, int codec, int threads);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,11 @@
-// attention.hip -- single-token (decode) paged attention over an ECC-protected
-// INT4 KV cache, decoding the codewords inline.
+// attention.hip -- paged attention over an ECC-protected INT4 KV cache, decoding
+// the codewords inline: kvecc_paged_attention (one query token per sequence,
+// the decode step) and kvecc_paged_attention_chunk (q_len tokens per sequence,
+// causal: a prefill, a chunk, a verify step's draft tokens; no reference
+// counterpart).  The chunked entry runs the same kernel bodies (attn_*_body.inc)
+// under kernel names of its own: the matrix-core kernels with 16 (token, head)
+// columns per workgroup and a per-column key limit (ChunkMap), the split
+// kernels over a virtual batch of batch * q_len rows (ChunkArgs).
 //
 // Reference: kv_cache/attention_ecc.py:265-427 (paged_attention_ecc_kernel,
 // Hamming(8,4) with decode_hamming84_inline :56-149 -- double errors keep their
@@ -105,6 +111,22 @@ struct AttnArgs {
   uint32_t *ctr;              // per-(batch, head group) split counters (attn_counter_slot), or
                               // null: a separate combine launch
 };
+
+// Chunked causal calls (kvecc_paged_attention_chunk) add their fields behind
+// AttnArgs and run kernels of their own names over the same bodies: the decode
+// kernels keep their argument block byte for byte (a longer one changed their
+// register allocation: 122 -> 134 VGPRs for the Hamming(8,4) matrix-core
+// kernel at head_dim 128, with no field of it read).  The split kernels see a
+// virtual batch of batch * q_len rows: row b' reads block-table row b' / q_len
+// and the keys before min(ctx_lens[b' / q_len] - q_len + 1 + b' % q_len, ctx_cap).
+struct ChunkArgs : AttnArgs {
+  uint32_t q_len;            // query tokens per sequence
+  uint32_t vb0;              // first virtual batch row of this launch (grids of > 65535 rows are sliced)
+  uint32_t cg_log2;          // matrix-core chunk kernels: log2 of the query heads per column group
+  int64_t q_sb, q_st, q_sh;  // query strides in elements: batch, token, head
+};
+template <typename A>
+constexpr bool is_chunk = std::is_same<A, ChunkArgs>::value;
 
 // Lane chunk c of a token row: VEC 32-bit words = 4*VEC H(8,4) codewords, or
 // VEC Golay codewords (3*VEC values; codewords past the row's last are read
@@ -478,296 +500,17 @@ __device__ void combine_if_last(const AttnArgs &a, int64_t bh0, float *wt) {
 // and decoded every cache row H/Hkv times.
 template <typename T, int CODEC, int VEC, int W, bool BUF, int G = 1, int UR = 0, int DEC = 0>
 __global__ __launch_bounds__(kBlock) void paged_attn_split_kernel(AttnArgs a) {
-  constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
-  using C = Chunk<CODEC, VEC>;
-  constexpr int E = C::E;
-  constexpr int TP = kBlock / W;  // token rows per pass (one per lane group)
-  // cache row of each token of the split (-1 = no block / past the split),
-  // padded so the unrolled loop reads it without bounds checks
-  // (UR > 0: another count, for the experiment forks)
-  constexpr int U = UR > 0                        ? UR
-                    : CODEC == KVECC_CODEC_GOLAY ? kGolayUnroll
-                    : CODEC == KVECC_CODEC_H84   ? kH84Unroll
-                                                 : kUnroll;
-  static_assert(U <= kMaxUnroll, "rows in flight");
-  __shared__ int32_t rows[kMaxSplit + (kMaxUnroll - 1) * kBlock];
-  // Golay tables copied from the device: the 32 KiB spread tables, or
-  // parity[4096] then correct[4096] as uint16 (16 KiB).  With the spread
-  // tables the block-table slice (before the copy) and the merge buffer (after
-  // the loop) live in the same LDS, which keeps 4 workgroups per CU.
-  constexpr bool kSpread = is_golay(CODEC);
-  // (DEC 2, the no-lookup probe: no tables, only the aliased block-table slice and merge buffer)
-  constexpr int kProbeWords = TP * W * E > kMaxSplit + 1 ? TP * W * E : kMaxSplit + 1;
-  constexpr int kTabWords = !is_golay(CODEC) ? 4 : (DEC & 2) ? kProbeWords : SP ? 4096 + 128 : kSpread ? 8192 : 4096;
-  static_assert(!kSpread || (TP * W * E <= kTabWords && kMaxSplit + 1 <= kTabWords), "LDS aliasing");
-  __shared__ __attribute__((aligned(16))) uint32_t gtab[kTabWords];
-  __shared__ float red_own[kSpread ? 1 : TP * W * E];  // per-group acc
-  float *red = kSpread ? reinterpret_cast<float *>(gtab) : red_own;
-  __shared__ float gml[2][TP];             // per-group running max / sum
-  __shared__ h84_lut_t lut[CODEC == KVECC_CODEC_H84 ? 256 : 1];  // H(8,4): codeword byte -> data - 8
-
-  const int64_t hgroups = a.heads / G;
-  const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;  // query heads h0 .. h0+G-1
-  const int64_t hk = h0 / (a.heads / a.kv_heads);
-  const int grp = threadIdx.x / W, c = threadIdx.x % W;
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);  // max_context_len and the table
-  const int64_t t0 = (int64_t)blockIdx.x * a.split;
-  const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
-  const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
-  const bool live = c < (a.g + VEC - 1) / VEC;  // lanes past the row idle
-  const int cs = live ? c : 0;
-  const int64_t ws_stride = a.nsplit * (a.d + 2);  // per query head
-  float *ws0 = a.ws + ((b * a.heads + h0) * a.nsplit + blockIdx.x) * (a.d + 2);
-  // this lane's query slice, issued before the block-table round trip (first
-  // used by the query sums after it)
-  float qv[G][E];
-  const float qscale = a.sm_scale * kAttnLogScale;
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int64_t di = (int64_t)c * E + e;
-      qv[j][e] = (live && di < a.d)
-                     ? to_f32<T>(reinterpret_cast<const T *>(a.q)[(b * a.heads + h0 + j) * a.d + di]) * qscale
-                     : 0.0f;
-    }
-  }
-
-  {  // block-table slice -> LDS (one load per logical block), then one 32-bit
-     // division per token; none in the streaming loop
-    __shared__ int32_t blks_own[kSpread ? 1 : kMaxSplit + 1];
-    int32_t *blks = kSpread ? reinterpret_cast<int32_t *>(gtab) : blks_own;
-    const uint32_t bs = (uint32_t)a.bs;
-    const uint32_t lb0 = (uint32_t)(t0 / a.bs);
-    // the whole split's slice, bounded by the table rather than the context, so
-    // the load does not wait for context_lens (one dependent HBM trip fewer)
-    const int64_t tmax = min<int64_t>(t0 + a.split, a.max_blocks * a.bs);
-    const int nlb = tmax > t0 ? (int)((uint32_t)(tmax - 1) / bs - lb0 + 1) : 0;
-    const int32_t *tab = a.table + b * a.max_blocks + lb0;
-    for (int j = threadIdx.x; j < nlb; j += kBlock) blks[j] = tab[j];
-    __syncthreads();
-    const int32_t head_row0 = (int32_t)((a.layer * a.kv_heads + hk) * a.bs);
-    const int32_t blk_rows = (int32_t)(a.layers * a.kv_heads * a.bs);
-    const int npad = (int)a.split + (U - 1) * kBlock;
-    for (int i = threadIdx.x; i < npad; i += kBlock) {
-      int32_t row = -1;
-      if (i < ntok) {
-        const uint32_t pos = (uint32_t)(t0 + i);
-        const uint32_t lb = pos / bs;
-        const int32_t blk = blks[lb - lb0];
-        if (blk >= 0) row = blk * blk_rows + head_row0 + (int32_t)(pos - lb * bs);
-      }
-      rows[i] = row;
-    }
-  }
-  if (kSpread && (DEC & 2)) {
-    __syncthreads();  // blks (aliased) fully read; the probe stages no tables
-  } else if (kSpread && SP) {
-    __syncthreads();  // blks (aliased) fully read
-    // the correction half, then T0[k] = P(k) and T1[k] = P(k << 6)
-    const u32x4 *src = reinterpret_cast<const u32x4 *>(a.atab_x + 4096);
-    u32x4 *dst = reinterpret_cast<u32x4 *>(gtab);
-#pragma unroll
-    for (int i = threadIdx.x; i < 1024; i += kBlock) dst[i] = src[i];
-    if (threadIdx.x < 128)
-      gtab[4096 + threadIdx.x] = a.atab_x[threadIdx.x < 64 ? threadIdx.x : (threadIdx.x - 64) << 6];
-  } else if (kSpread) {
-    __syncthreads();  // blks (aliased) fully read
-    const u32x4 *src = reinterpret_cast<const u32x4 *>(a.atab_x);
-    u32x4 *dst = reinterpret_cast<u32x4 *>(gtab);
-#pragma unroll
-    for (int i = threadIdx.x; i < 2048; i += kBlock) dst[i] = src[i];
-  } else if (is_golay(CODEC)) {
-    const u32x4 *src0 = reinterpret_cast<const u32x4 *>(a.par);
-    const u32x4 *src1 = reinterpret_cast<const u32x4 *>(a.cor);
-    u32x4 *dst = reinterpret_cast<u32x4 *>(gtab);
-    for (int i = threadIdx.x; i < 512; i += kBlock) {
-      dst[i] = src0[i];
-      dst[512 + i] = src1[i];
-    }
-  }
-  if (CODEC == KVECC_CODEC_H84 && threadIdx.x < 256) {
-    uint32_t q, t, n1 = 0, n2 = 0;
-    h84_decode4(threadIdx.x, q, t, n1, n2);
-    lut[threadIdx.x] = (h84_lut_t)((int)(q & 0xFu) - 8);
-  }
-  float qsum[G];  // sum of this lane's q (folds the decode's kOffset out of the K sums)
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-    qsum[j] = 0.0f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) qsum[j] += qv[j][e];
-    if (C::kThird16) {  // decode's 16 n in slots 3k + 2 (after the sum: it folds n - 8)
-#pragma unroll
-      for (int e = 2; e < E; e += 3) qv[j][e] *= 0.0625f;
-    }
-  }
-  __syncthreads();
-
-  // buffer descriptors (BUF kernels; dead code otherwise)
-  const __amdgpu_buffer_rsrc_t krs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.k_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.v_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t ksrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.k_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vsrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.v_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  // ---- one pass: U K and V rows in flight per lane, online softmax per group
-  // (and per query head j of the workgroup)
-  float m[G], l[G], acc[G][E];
-  float psum[G];  // sum of p * v_scale, for the kOffset fold of the V sums
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-    m[j] = -INFINITY;
-    l[j] = 0.0f;
-    psum[j] = 0.0f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) acc[j][e] = 0.0f;
-  }
-  // GQA workgroups (G > 1) do G times the arithmetic per row and have a
-  // quarter of MHA's rows: they issue the next iteration's rows before using
-  // this one's (MHA measured no gain from that in round 1)
-  constexpr bool kPrefetch = G > 1 && CODEC == KVECC_CODEC_H84;
-  C pkc[U], pvc[U];
-  float pks[U], pvs[U];
-  bool pok[U];
-  auto load_rows = [&](int i0) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {  // branch-free: invalid rows read row 0, masked
-      const int32_t r = rows[i0 + u * TP];
-      pok[u] = r >= 0;
-      const int64_t row = pok[u] ? r : 0;
-      if (BUF) {
-        pkc[u].load_buf(a, krs, (int32_t)row, cs);
-        pvc[u].load_buf(a, vrs, (int32_t)row, cs);
-        pks[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ksrs, (uint32_t)row * 4u, 0, 0));
-        pvs[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vsrs, (uint32_t)row * 4u, 0, 0));
-      } else {
-        pkc[u].load(a, a.k_cache, row, cs);
-        pvc[u].load(a, a.v_cache, row, cs);
-        pks[u] = a.k_scales[row];
-        pvs[u] = a.v_scales[row];
-      }
-    }
-  };
-  if (kPrefetch && grp < ntok) load_rows(grp);
-  for (int i0 = grp; i0 < ntok; i0 += TP * U) {
-    if (!kPrefetch) load_rows(i0);
-    C kc[U], vc[U];
-    float ks[U], vs[U];
-    bool ok[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      kc[u] = pkc[u];
-      vc[u] = pvc[u];
-      ks[u] = pks[u];
-      vs[u] = pvs[u];
-      ok[u] = pok[u];
-    }
-    if (kPrefetch && i0 + TP * U < ntok) load_rows(i0 + TP * U);
-    float sc[G][U];
-    float mn[G];
-#pragma unroll
-    for (int j = 0; j < G; ++j) mn[j] = m[j];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float part[G];
-#pragma unroll
-      for (int j = 0; j < G; ++j) part[j] = 0.0f;
-      if (live) {
-        float kv[E];
-        kc[u].template decode<DEC>(lut, gtab, kv);
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          part[j] = dot<E>(qv[j], kv);
-          if (C::kOffset != 0.0f) part[j] -= C::kOffset * qsum[j];
-          part[j] *= ks[u];  // sum q (n - 8) s = s * sum q (n - 8)
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        part[j] = group_sum<W>(part[j]);
-        sc[j][u] = ok[u] ? part[j] : -INFINITY;
-        mn[j] = fmaxf(mn[j], sc[j][u]);
-      }
-    }
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < G; ++j) any |= mn[j] != -INFINITY;
-    if (!any) continue;  // no valid row yet (uniform per group)
-    float ps[G][U];
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      if (G > 1 && mn[j] == -INFINITY) {  // this head has no finite score yet: no update
-#pragma unroll
-        for (int u = 0; u < U; ++u) ps[j][u] = 0.0f;
-        continue;
-      }
-      const float alpha = attn_exp(m[j] - mn[j]);  // m = -inf -> 0
-      l[j] *= alpha;
-      psum[j] *= alpha;
-#pragma unroll
-      for (int e = 0; e < E; ++e) acc[j][e] *= alpha;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const float p = attn_exp(sc[j][u] - mn[j]);  // invalid rows: exp(-inf) = 0
-        l[j] += p;
-        ps[j][u] = p * vs[u];
-        psum[j] += ps[j][u];
-      }
-      m[j] = mn[j];
-    }
-    if (live) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        float vv[E];
-        vc[u].template decode<DEC>(lut, gtab, vv);
-#pragma unroll
-        for (int j = 0; j < G; ++j) axpy<E>(acc[j], ps[j][u], vv);
-      }
-    }
-  }
-
-  // ---- merge the TP groups (one query head at a time) ------------------------------
-  if (kSpread) __syncthreads();  // the tables (aliased by red) fully read
-  __shared__ float gw[TP];  // e^(m_g - M) per group
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-    if (j > 0) __syncthreads();  // the previous head's merge fully read red / gml / gw
-    if (live) {
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const float ae = C::kThird16 && e % 3 == 2 ? acc[j][e] * 0.0625f : acc[j][e];  // 16 n slots
-        red[(grp * W + c) * E + e] = C::kOffset != 0.0f ? ae - C::kOffset * psum[j] : ae;
-      }
-    }
-    if (c == 0) {
-      gml[0][grp] = m[j];
-      gml[1][grp] = l[j];
-    }
-    __syncthreads();
-    float M = -INFINITY;
-    for (int gi = 0; gi < TP; ++gi) M = fmaxf(M, gml[0][gi]);
-    if (threadIdx.x < TP) {
-      const float mg = gml[0][threadIdx.x];
-      gw[threadIdx.x] = mg == -INFINITY ? 0.0f : attn_exp(mg - M);
-    }
-    __syncthreads();
-    float *ws = ws0 + j * ws_stride;
-    for (int64_t di = threadIdx.x; di < a.d; di += kBlock) {
-      float sum = 0.0f;
-      for (int gi = 0; gi < TP; ++gi) sum += red[gi * W * E + di] * gw[gi];
-      ws_put(ws + 2 + di, sum);
-    }
-    if (threadIdx.x == 0) {
-      float L = 0.0f;
-      for (int gi = 0; gi < TP; ++gi) L += gml[1][gi] * gw[gi];
-      ws_put(ws, M);
-      ws_put(ws + 1, L);
-    }
-  }
-  if (a.ctr) combine_if_last<T, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));
+#define ATTN_BODY_CHUNK 0
+#include "attn_split_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+// the general path of a chunked call: the same body over the virtual batch (ChunkArgs)
+template <typename T, int CODEC, int VEC, int W, bool BUF, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_chunk_kernel(ChunkArgs a) {
+  constexpr int UR = 0, DEC = 0;
+#define ATTN_BODY_CHUNK 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_CHUNK
 }
 
 // ---- GQA on the matrix cores (Hamming(8,4), fp16 queries) -----------------------
@@ -846,234 +589,67 @@ __device__ __forceinline__ void load_chunk(__amdgpu_buffer_rsrc_t rs, uint32_t o
   }
 }
 
+// What a column of a matrix-core chunk kernel stands for.  The decode kernels'
+// column n is query head h0 + n of the workgroup's G (blockIdx.y = (batch, head
+// group), blockIdx.x = split), and every column sees the sequence's whole
+// context.  The chunk kernels use all 16 columns: with cg = 2^cg_log2 query
+// heads sharing the cache head, column n is chunk token tq = (16 / cg) tile +
+// n / cg and head h0 + n % cg, blockIdx.x = tile * nsplit + split.  Token tq
+// sits at position context_len - q_len + tq and sees the keys at or before it:
+// its key limit is that position + 1, clamped to [0, ctx_cap]; the workgroup
+// walks the split up to the tile's largest limit (its last token's), each lane
+// masks the scores at or past its own column's.  A masked score is -inf like a
+// -1 block's, so it has no weight in l, psum (the -8 fold) or the accumulators,
+// and a column with nothing to see in this split leaves m = -inf, l = 0.
+struct ChunkMap {
+  int64_t b, h0, ctx;
+  uint32_t split_idx, tile, tq, hq;
+  bool col_ok;  // the column holds a query row
+  int64_t lim;  // this column's key limit (absolute)
+  __device__ __forceinline__ ChunkMap(const ChunkArgs &a, int n) {
+    const uint32_t hgroups = (uint32_t)a.heads >> a.cg_log2;
+    b = blockIdx.y / hgroups;
+    h0 = (int64_t)(blockIdx.y % hgroups) << a.cg_log2;
+    tile = blockIdx.x / (uint32_t)a.nsplit;
+    split_idx = blockIdx.x - tile * (uint32_t)a.nsplit;
+    const uint32_t tpt = 16u >> a.cg_log2;  // tokens per tile
+    tq = tile * tpt + ((uint32_t)n >> a.cg_log2);
+    hq = (uint32_t)h0 + ((uint32_t)n & ((1u << a.cg_log2) - 1u));
+    col_ok = tq < a.q_len;
+    const int64_t first = (int64_t)a.ctx_lens[b] - a.q_len + 1;  // token 0's key limit
+    const uint32_t tlast = min(tile * tpt + tpt - 1u, a.q_len - 1u);
+    ctx = min<int64_t>(first + tlast, a.ctx_cap);
+    lim = col_ok ? min<int64_t>(first + tq, a.ctx_cap) : 0;
+  }
+  // the column's limit relative to the split's first token t0, as an int the
+  // lanes compare token indices against (clamped: a split has <= kMaxSplit tokens)
+  __device__ __forceinline__ int col_limit(int64_t t0) const {
+    return (int)max<int64_t>(min<int64_t>(lim - t0, kMaxSplit + kMfmaStep), 0);
+  }
+  __device__ __forceinline__ const __half *q_row(const ChunkArgs &a) const {
+    return reinterpret_cast<const __half *>(a.q) + b * a.q_sb + tq * a.q_st + hq * a.q_sh;
+  }
+  // output (and workspace) row of column h of the workgroup; -1: no query row there
+  __device__ __forceinline__ int64_t out_row(const ChunkArgs &a, int h) const {
+    const uint32_t t = tile * (16u >> a.cg_log2) + ((uint32_t)h >> a.cg_log2);
+    if (t >= a.q_len) return -1;
+    return (b * a.q_len + t) * a.heads + h0 + ((uint32_t)h & ((1u << a.cg_log2) - 1u));
+  }
+};
+
 template <int D, int G>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_kernel(AttnArgs a) {
-  constexpr int KK = D / 32;  // QK MFMAs per 16-token tile
-  constexpr int MT = D / 16;  // PV M-tiles; V bytes per lane per token
-  constexpr int KB = D / 4;   // K bytes per lane per token
-  constexpr int VW = MT >= 4 ? MT / 4 : 1;  // V dwords per token
-  constexpr int kWaves = kBlock / kWave;
-  __shared__ __attribute__((aligned(16))) int32_t rows[kMaxSplit + kMfmaStep];
-  __shared__ int32_t blks[kMaxSplit + 1];
-  __shared__ uint8_t lut[256];
-  __shared__ float red[kWaves][G][D];
-  __shared__ float gml[2][kWaves][G];
-
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int n = lane & 15, g = lane >> 4;
-  const int64_t hgroups = a.heads / G;
-  const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;
-  const int64_t hk = h0 / (a.heads / a.kv_heads);
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);
-  const int64_t t0 = (int64_t)blockIdx.x * a.split;
-  const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
-  const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
-  // Q^T operand (B): column n = head h0 + n, k-slot 8g + j of MFMA kk = d (D/4)g + 8kk + j.
-  // Issued first: it lands during the block-table round trip instead of
-  // after it (its first use, the query sum, precedes the first K/V loads)
-  f16x8 qop[KK];
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk) {
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (n < G)
-      v = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const __half *>(a.q) +
-                                           (b * a.heads + h0 + n) * D + KB * g + 8 * kk);
-    qop[kk] = __builtin_bit_cast(f16x8, v);
-  }
-  {  // block-table slice -> cache rows (-1: no block / past the split)
-    const uint32_t bs = (uint32_t)a.bs;
-    const uint32_t lb0 = (uint32_t)(t0 / a.bs);
-    // the whole split's slice, bounded by the table rather than the context, so
-    // the load does not wait for context_lens (one dependent HBM trip fewer)
-    const int64_t tmax = min<int64_t>(t0 + a.split, a.max_blocks * a.bs);
-    const int nlb = tmax > t0 ? (int)((uint32_t)(tmax - 1) / bs - lb0 + 1) : 0;
-    const int32_t *tab = a.table + b * a.max_blocks + lb0;
-    for (int j = threadIdx.x; j < nlb; j += kBlock) blks[j] = tab[j];
-    __syncthreads();
-    const int32_t head_row0 = (int32_t)((a.layer * a.kv_heads + hk) * a.bs);
-    const int32_t blk_rows = (int32_t)(a.layers * a.kv_heads * a.bs);
-    const int npad = (ntok + kMfmaStep - 1) / kMfmaStep * kMfmaStep;
-    for (int i = threadIdx.x; i < npad; i += kBlock) {
-      int32_t row = -1;
-      if (i < ntok) {
-        const uint32_t pos = (uint32_t)(t0 + i);
-        const uint32_t lb = pos / bs;
-        const int32_t blk = blks[lb - lb0];
-        if (blk >= 0) row = blk * blk_rows + head_row0 + (int32_t)(pos - lb * bs);
-      }
-      rows[i] = row;
-    }
-  }
-  {
-    uint32_t dq, dt, n1 = 0, n2 = 0;
-    h84_decode4(threadIdx.x, dq, dt, n1, n2);  // kBlock == 256: one table entry per thread
-    lut[threadIdx.x] = (uint8_t)(dq & 0xFu);
-  }
-  float qsum = 0.0f;  // sum of head n's query over all d (the offset fold)
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qsum += (float)qop[kk][e];
-  qsum += __shfl_xor(qsum, 16, kWave);
-  qsum += __shfl_xor(qsum, 32, kWave);
-  __syncthreads();
-
-  const __amdgpu_buffer_rsrc_t krs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.k_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.v_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t ksrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.k_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vsrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.v_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  const float qscale = a.sm_scale * kAttnLogScale;
-  f32x4 acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  float m = -INFINITY, l = 0.0f;
-  float psum = 0.0f;  // sum of p * v_scale over this lane's tokens (the offset fold)
-  const float qoff = kMfmaValOffset * qsum;
-
-  // one step's operands in registers: 2 K rows (tokens i0 + n, i0 + 16 + n),
-  // 8 V rows and scales (tokens i0 + 16(j >> 2) + 4g + (j & 3)); invalid rows
-  // read row 0 and are masked
-  struct Step {
-    int32_t rv[8];
-    uint32_t kw[2][KB / 4 > 0 ? KB / 4 : 1];
-    uint32_t vw[8][VW];
-    float ks[8], vs[8];
-  };
-  auto load_step = [&](int i0, Step &st) {
-    const int4 r0 = *reinterpret_cast<const int4 *>(&rows[i0 + 4 * g]);
-    const int4 r1 = *reinterpret_cast<const int4 *>(&rows[i0 + 16 + 4 * g]);
-    st.rv[0] = r0.x; st.rv[1] = r0.y; st.rv[2] = r0.z; st.rv[3] = r0.w;
-    st.rv[4] = r1.x; st.rv[5] = r1.y; st.rv[6] = r1.z; st.rv[7] = r1.w;
-#pragma unroll
-    for (int tau = 0; tau < 2; ++tau) {
-      const int32_t r = rows[i0 + 16 * tau + n];
-      load_chunk<KB>(krs, (uint32_t)max(r, 0) * (uint32_t)D + (uint32_t)(KB * g), st.kw[tau]);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t r = (uint32_t)max(st.rv[j], 0);
-      load_chunk<MT>(vrs, r * (uint32_t)D + (uint32_t)(MT * n), st.vw[j]);
-      st.ks[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ksrs, r * 4u, 0, 0));
-      st.vs[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vsrs, r * 4u, 0, 0));
-    }
-  };
-  constexpr int kStride = kWaves * kMfmaStep;
-  for (int i0 = wave * kMfmaStep; i0 < ntok; i0 += kStride) {
-    Step cur;
-    load_step(i0, cur);
-    const int32_t *rv = cur.rv;
-    const float *ks = cur.ks, *vs = cur.vs;
-    auto &kw = cur.kw;
-    auto &vw = cur.vw;
-    // ---- S^T = K . Q^T, two 16-token tiles
-    f32x4 S[2];
-#pragma unroll
-    for (int tau = 0; tau < 2; ++tau) {
-      S[tau] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk) {
-        uint32_t p[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {  // bytes 8kk + 2h, 8kk + 2h + 1
-          const uint32_t w = kw[tau][2 * kk + h / 2];
-          const int sh = 16 * (h & 1);
-          p[h] = nib_pair_f16(lut[(w >> sh) & 0xFFu], lut[(w >> (sh + 8)) & 0xFFu]);
-        }
-        S[tau] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, u32x4{p[0], p[1], p[2], p[3]}),
-                                                        qop[kk], S[tau], 0, 0, 0);
-      }
-    }
-    // ---- online softmax over this lane's 8 tokens of head n
-    float s[8];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s[j] = rv[j] >= 0 ? (S[j >> 2][j & 3] * kMfmaValScale - qoff) * (qscale * ks[j]) : -INFINITY;
-      mx = fmaxf(mx, s[j]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, kWave));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
-    const float mn = fmaxf(m, mx);
-    const float mu = mn == -INFINITY ? 0.0f : mn;  // no valid token yet: nothing to scale
-    const float alpha = attn_exp(m - mu);
-    m = mn;
-    l *= alpha;
-    psum *= alpha;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] *= alpha;
-    uint32_t phi[4], plo[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float p0 = attn_exp(s[2 * h] - mu), p1 = attn_exp(s[2 * h + 1] - mu);
-      l += p0 + p1;
-      const float w0 = p0 * vs[2 * h], w1 = p1 * vs[2 * h + 1];
-      psum += w0 + w1;
-      const auto hi = __builtin_amdgcn_cvt_pkrtz(w0, w1);
-      const auto lo = __builtin_amdgcn_cvt_pkrtz(w0 - (float)hi[0], w1 - (float)hi[1]);
-      phi[h] = __builtin_bit_cast(uint32_t, hi);
-      plo[h] = __builtin_bit_cast(uint32_t, lo);
-    }
-    const f16x8 pb_hi = __builtin_bit_cast(f16x8, u32x4{phi[0], phi[1], phi[2], phi[3]});
-    const f16x8 pb_lo = __builtin_bit_cast(f16x8, u32x4{plo[0], plo[1], plo[2], plo[3]});
-    // ---- O^T += V^T . P: M-tile mt takes byte mt of each token's chunk
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      uint32_t p[4];
-#pragma unroll
-      for (int h = 0; h < 4; ++h) {  // tokens j = 2h, 2h + 1
-        const int sh = 8 * (mt & 3);
-        p[h] = nib_pair_f16(lut[(vw[2 * h][mt / 4] >> sh) & 0xFFu], lut[(vw[2 * h + 1][mt / 4] >> sh) & 0xFFu]);
-      }
-      const f16x8 va = __builtin_bit_cast(f16x8, u32x4{p[0], p[1], p[2], p[3]});
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(va, pb_hi, acc[mt], 0, 0, 0);
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(va, pb_lo, acc[mt], 0, 0, 0);
-    }
-  }
-
-  // ---- merge: the 4 lanes of a head, then the workgroup's waves
-  l += __shfl_xor(l, 16, kWave);
-  l += __shfl_xor(l, 32, kWave);
-  psum += __shfl_xor(psum, 16, kWave);
-  psum += __shfl_xor(psum, 32, kWave);
-  const float poff = kMfmaValOffset * psum;
-  if (n < G) {
-    if (g == 0) {
-      gml[0][wave][n] = m;
-      gml[1][wave][n] = l;
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][n][MT * (4 * g + r) + mt] = acc[mt][r] * kMfmaValScale - poff;
-  }
-  __syncthreads();
-  const int64_t ws_stride = a.nsplit * (a.d + 2);
-  float *ws0 = a.ws + ((b * a.heads + h0) * a.nsplit + blockIdx.x) * (a.d + 2);
-  for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
-    const int h = idx / D, d = idx % D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) M = fmaxf(M, gml[0][w][h]);
-    float o = 0.0f, L = 0.0f;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const float mw = gml[0][w][h];
-      const float wt = mw == -INFINITY ? 0.0f : attn_exp(mw - M);
-      o += red[w][h][d] * wt;
-      L += gml[1][w][h] * wt;
-    }
-    float *ws = ws0 + h * ws_stride;
-    ws_put(ws + 2 + d, o);
-    if (d == 0) {
-      ws_put(ws, M);
-      ws_put(ws + 1, L);
-    }
-  }
-  if (a.ctr) combine_if_last<__half, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));
+#define ATTN_BODY_CHUNK 0
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+// the chunked causal form: 16 (token, head) columns per workgroup (ChunkMap)
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_chunk_kernel(ChunkArgs a) {
+  constexpr int G = 16;
+#define ATTN_BODY_CHUNK 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
 }
 
 // ---- GQA on the matrix cores, Golay(24,12) int32 caches, head_dim 128 ---------
@@ -1098,283 +674,16 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_kernel(AttnArgs
 // the row's 129 belong to d >= 128 (q = 0, outputs discarded).
 template <int G, bool PACKED>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_kernel(AttnArgs a) {
-  constexpr int D = 128, GC = 43;          // head_dim, codewords per row
-  constexpr int KC = PACKED ? 12 : 11;     // K codewords per lane group
-  constexpr int KD = 3 * KC, KK = 5;       // its values; QK MFMAs per 16 tokens
-  constexpr int VC = 3, MT = 9;            // V codewords per lane; PV M-tiles
-  constexpr int KW = PACKED ? 9 : KC;      // K dwords per lane group
-  constexpr uint32_t kRowBytes = PACKED ? KVECC_GOLAY_PACKED_ROW(GC) : GC * 4;
-  constexpr int kWaves = kBlock / kWave;
-  __shared__ __attribute__((aligned(16))) uint32_t gt[8192];  // spread tables (golay_attn_table_dev)
-  __shared__ __attribute__((aligned(16))) int32_t rows[kMaxSplit + kMfmaStep];
-  __shared__ int32_t blks[kMaxSplit + 1];
-  __shared__ float red[kWaves][G][D];
-  __shared__ float gml[2][kWaves][G];
-
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int n = lane & 15, g = lane >> 4;
-  const int64_t hgroups = a.heads / G;
-  const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;
-  const int64_t hk = h0 / (a.heads / a.kv_heads);
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);
-  const int64_t t0 = (int64_t)blockIdx.x * a.split;
-  const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
-  const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
-  // Q^T operand: k-slot v = 8kk + j of lane group g is d = KD g + v (v < KD, d < 128), else 0;
-  // issued before the block-table round trip, as in the H(8,4) kernel
-  f16x8 qop[KK];
-  {
-    const __half *qh = reinterpret_cast<const __half *>(a.q) + (b * a.heads + h0 + n) * D;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int v = 8 * kk + j, d = KD * g + v;
-        _Float16 x = 0;
-        if (n < G && v < KD && d < D) x = __builtin_bit_cast(_Float16, qh[d]);
-        qop[kk][j] = x;
-      }
-    }
-  }
-  {  // block-table slice -> cache rows, as in the H(8,4) kernel
-    const uint32_t bs = (uint32_t)a.bs;
-    const uint32_t lb0 = (uint32_t)(t0 / a.bs);
-    const int64_t tmax = min<int64_t>(t0 + a.split, a.max_blocks * a.bs);
-    const int nlb = tmax > t0 ? (int)((uint32_t)(tmax - 1) / bs - lb0 + 1) : 0;
-    const int32_t *tab = a.table + b * a.max_blocks + lb0;
-    for (int j = threadIdx.x; j < nlb; j += kBlock) blks[j] = tab[j];
-    {
-      const u32x4 *src = reinterpret_cast<const u32x4 *>(a.atab);
-      for (int i = threadIdx.x; i < 2048; i += kBlock) reinterpret_cast<u32x4 *>(gt)[i] = src[i];
-    }
-    __syncthreads();
-    const int32_t head_row0 = (int32_t)((a.layer * a.kv_heads + hk) * a.bs);
-    const int32_t blk_rows = (int32_t)(a.layers * a.kv_heads * a.bs);
-    const int npad = (ntok + kMfmaStep - 1) / kMfmaStep * kMfmaStep;
-    for (int i = threadIdx.x; i < npad; i += kBlock) {
-      int32_t row = -1;
-      if (i < ntok) {
-        const uint32_t pos = (uint32_t)(t0 + i);
-        const uint32_t lb = pos / bs;
-        const int32_t blk = blks[lb - lb0];
-        if (blk >= 0) row = blk * blk_rows + head_row0 + (int32_t)(pos - lb * bs);
-      }
-      rows[i] = row;
-    }
-  }
-  float qsum = 0.0f;
-  {
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) qsum += (float)qop[kk][j];
-    qsum += __shfl_xor(qsum, 16, kWave);
-    qsum += __shfl_xor(qsum, 32, kWave);
-  }
-  __syncthreads();
-
-  // codeword -> data nibbles one per byte (bytes 0..2), uncorrectable words keep
-  // their data.  (The split kernels' table, parity at the codeword's parity
-  // bits and the nibbles in bytes 0, 1, 3, measured 1 % slower here:
-  // profiles/r04/attn/xtab_ab.log.)
-  auto sp_of = [&](uint32_t c) -> uint32_t {
-    const uint32_t p = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(gt) + ((c << 2) & 0x3FFCu));
-    const uint32_t off = ((c >> 10) ^ (p >> 18)) & 0x3FFCu;
-    const uint32_t e = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(gt + 4096) + off);
-    return __builtin_amdgcn_bitop3_b32(p, e, 0x000F0F0Fu, 0x28);  // (p ^ e) & mask
-  };
-  // f16 subnormal pair: byte e0 of lo (0x0c: zero), byte e1 of hi, in halves 0 and 1
-  auto pair = [](uint32_t hi, uint32_t lo, int e0, int e1) -> uint32_t {
-    const uint32_t s0 = e0 < 0 ? 0x0cu : (uint32_t)e0, s1 = e1 < 0 ? 0x0cu : (uint32_t)(4 + e1);
-    return __builtin_amdgcn_perm(hi, lo, 0x0c000c00u | s1 << 16 | s0);
-  };
-
-  const __amdgpu_buffer_rsrc_t krs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.k_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.v_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t ksrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.k_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vsrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.v_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  constexpr float kScale = 16777216.0f, kOff = 8.0f;  // subnormal operands: 2^24, and n - 8
-  const float qscale = a.sm_scale * kAttnLogScale;
-  const float qoff = kOff * qsum;
-  f32x4 acc[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  float m = -INFINITY, l = 0.0f, psum = 0.0f;
-
-  for (int i0 = wave * kMfmaStep; i0 < ntok; i0 += kWaves * kMfmaStep) {
-    int32_t rv[8];
-    {
-      const int4 r0 = *reinterpret_cast<const int4 *>(&rows[i0 + 4 * g]);
-      const int4 r1 = *reinterpret_cast<const int4 *>(&rows[i0 + 16 + 4 * g]);
-      rv[0] = r0.x; rv[1] = r0.y; rv[2] = r0.z; rv[3] = r0.w;
-      rv[4] = r1.x; rv[5] = r1.y; rv[6] = r1.z; rv[7] = r1.w;
-    }
-    uint32_t kw[2][KW];
-#pragma unroll
-    for (int tau = 0; tau < 2; ++tau) {
-      const uint32_t off = (uint32_t)max(rows[i0 + 16 * tau + n], 0) * kRowBytes + 4u * KW * g;
-      const u32x4 x0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off, 0, 0));
-      const u32x4 x1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, off + 16, 0, 0));
-      kw[tau][0] = x0.x; kw[tau][1] = x0.y; kw[tau][2] = x0.z; kw[tau][3] = x0.w;
-      kw[tau][4] = x1.x; kw[tau][5] = x1.y; kw[tau][6] = x1.z; kw[tau][7] = x1.w;
-      if constexpr (PACKED) {
-        kw[tau][8] = __builtin_amdgcn_raw_buffer_load_b32(krs, off + 32, 0, 0);
-      } else {
-        const auto x2 = __builtin_amdgcn_raw_buffer_load_b96(krs, off + 32, 0, 0);
-        kw[tau][8] = x2[0]; kw[tau][9] = x2[1]; kw[tau][10] = x2[2];
-      }
-    }
-    // V: this lane's codewords start 12n bytes (int32) or 9n bytes (packed) into the row
-    const uint32_t voff = PACKED ? (9u * n) & ~3u : 12u * n;
-    const uint32_t vsh = n & 3;  // packed: byte of the first codeword in the loaded dword
-    uint32_t vw[8][VC];
-    float ks[8], vs[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t r = (uint32_t)max(rv[j], 0);
-      const auto x = __builtin_amdgcn_raw_buffer_load_b96(vrs, r * kRowBytes + voff, 0, 0);
-      vw[j][0] = x[0]; vw[j][1] = x[1]; vw[j][2] = x[2];
-      ks[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ksrs, r * 4u, 0, 0));
-      vs[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(vsrs, r * 4u, 0, 0));
-    }
-    // ---- S^T = K . Q^T
-    f32x4 S[2];
-#pragma unroll
-    for (int tau = 0; tau < 2; ++tau) {
-      uint32_t cw[KC];
-      if constexpr (PACKED) {  // 4 little-endian 3-byte codewords per 3 dwords
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          const uint32_t d0 = kw[tau][3 * t], d1 = kw[tau][3 * t + 1], d2 = kw[tau][3 * t + 2];
-          cw[4 * t] = d0;
-          cw[4 * t + 1] = __builtin_amdgcn_alignbyte(d1, d0, 3);
-          cw[4 * t + 2] = __builtin_amdgcn_alignbyte(d2, d1, 2);
-          cw[4 * t + 3] = d2 >> 8;
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < KC; ++c) cw[c] = kw[tau][c];
-      }
-      uint32_t sp[KC];
-#pragma unroll
-      for (int c = 0; c < KC; ++c) sp[c] = sp_of(cw[c]);
-      S[tau] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int kk = 0; kk < KK; ++kk) {
-        uint32_t p[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-          const int v0 = 8 * kk + 2 * h, v1 = v0 + 1;
-          const int c0 = v0 < KD ? v0 / 3 : 0, c1 = v1 < KD ? v1 / 3 : 0;
-          p[h] = pair(sp[c1], sp[c0], v0 < KD ? v0 % 3 : -1, v1 < KD ? v1 % 3 : -1);
-        }
-        S[tau] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, u32x4{p[0], p[1], p[2], p[3]}),
-                                                        qop[kk], S[tau], 0, 0, 0);
-      }
-    }
-    // ---- online softmax over this lane's 8 tokens of head n
-    float s[8];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s[j] = rv[j] >= 0 ? (S[j >> 2][j & 3] * kScale - qoff) * (qscale * ks[j]) : -INFINITY;
-      mx = fmaxf(mx, s[j]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, kWave));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
-    const float mn = fmaxf(m, mx);
-    const float mu = mn == -INFINITY ? 0.0f : mn;
-    const float alpha = attn_exp(m - mu);
-    m = mn;
-    l *= alpha;
-    psum *= alpha;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] *= alpha;
-    uint32_t phi[4], plo[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float p0 = attn_exp(s[2 * h] - mu), p1 = attn_exp(s[2 * h + 1] - mu);
-      l += p0 + p1;
-      const float w0 = p0 * vs[2 * h], w1 = p1 * vs[2 * h + 1];
-      psum += w0 + w1;
-      const auto hi = __builtin_amdgcn_cvt_pkrtz(w0, w1);
-      const auto lo = __builtin_amdgcn_cvt_pkrtz(w0 - (float)hi[0], w1 - (float)hi[1]);
-      phi[h] = __builtin_bit_cast(uint32_t, hi);
-      plo[h] = __builtin_bit_cast(uint32_t, lo);
-    }
-    const f16x8 pb_hi = __builtin_bit_cast(f16x8, u32x4{phi[0], phi[1], phi[2], phi[3]});
-    const f16x8 pb_lo = __builtin_bit_cast(f16x8, u32x4{plo[0], plo[1], plo[2], plo[3]});
-    // ---- O^T += V^T . P: tile mt takes nibble mt % 3 of codeword mt / 3
-    uint32_t sv[8][VC];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if constexpr (PACKED) {  // codeword c at byte vsh + 3c of the 12 loaded (alignbyte uses shift & 3)
-        const uint32_t d0 = vw[j][0], d1 = vw[j][1], d2 = vw[j][2];
-        vw[j][0] = __builtin_amdgcn_alignbyte(d1, d0, vsh);
-        vw[j][1] = __builtin_amdgcn_alignbyte(vsh ? d2 : d1, vsh ? d1 : d0, vsh + 3);
-        vw[j][2] = __builtin_amdgcn_alignbyte(d2, vsh < 2 ? d1 : d2, vsh + 2);
-      }
-#pragma unroll
-      for (int c = 0; c < VC; ++c) sv[j][c] = sp_of(vw[j][c]);
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      uint32_t p[4];
-#pragma unroll
-      for (int h = 0; h < 4; ++h) p[h] = pair(sv[2 * h + 1][mt / 3], sv[2 * h][mt / 3], mt % 3, mt % 3);
-      const f16x8 va = __builtin_bit_cast(f16x8, u32x4{p[0], p[1], p[2], p[3]});
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(va, pb_hi, acc[mt], 0, 0, 0);
-      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(va, pb_lo, acc[mt], 0, 0, 0);
-    }
-  }
-
-  // ---- merge, as in the H(8,4) kernel
-  l += __shfl_xor(l, 16, kWave);
-  l += __shfl_xor(l, 32, kWave);
-  psum += __shfl_xor(psum, 16, kWave);
-  psum += __shfl_xor(psum, 32, kWave);
-  const float poff = kOff * psum;
-  if (n < G) {
-    if (g == 0) {
-      gml[0][wave][n] = m;
-      gml[1][wave][n] = l;
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int d = MT * (4 * g + r) + mt;
-        if (d < D) red[wave][n][d] = acc[mt][r] * kScale - poff;
-      }
-  }
-  __syncthreads();
-  const int64_t ws_stride = a.nsplit * (a.d + 2);
-  float *ws0 = a.ws + ((b * a.heads + h0) * a.nsplit + blockIdx.x) * (a.d + 2);
-  for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
-    const int h = idx / D, d = idx % D;
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) M = fmaxf(M, gml[0][w][h]);
-    float o = 0.0f, L = 0.0f;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const float mw = gml[0][w][h];
-      const float wt = mw == -INFINITY ? 0.0f : attn_exp(mw - M);
-      o += red[w][h][d] * wt;
-      L += gml[1][w][h] * wt;
-    }
-    float *ws = ws0 + h * ws_stride;
-    ws_put(ws + 2 + d, o);
-    if (d == 0) {
-      ws_put(ws, M);
-      ws_put(ws + 1, L);
-    }
-  }
-  if (a.ctr) combine_if_last<__half, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));
+#define ATTN_BODY_CHUNK 0
+#include "attn_golay_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <bool PACKED>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_chunk_kernel(ChunkArgs a) {
+  constexpr int G = 16;
+#define ATTN_BODY_CHUNK 1
+#include "attn_golay_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
 }
 
 template <typename T>
@@ -1391,13 +700,23 @@ static int pow2_at_least(int64_t x) {
   return w;
 }
 
-template <typename T, int CODEC, int VEC, bool BUF>
-static int launch_split_w(const AttnArgs &a, dim3 grid, hipStream_t st) {
+// the split kernel of the argument type: the decode entry's (AttnArgs) or the
+// chunked call's over its virtual batch (ChunkArgs)
+#define KVECC_SPLIT_LAUNCH(VEC_, WW, BUF_, G_)                                                                  \
+  do {                                                                                                          \
+    if constexpr (is_chunk<A>)                                                                                  \
+      KVECC_LAUNCH((paged_attn_split_chunk_kernel<T, CODEC, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
+    else                                                                                                        \
+      KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
+  } while (0)
+
+template <typename T, int CODEC, int VEC, bool BUF, typename A>
+static int launch_split_w(const A &a, dim3 grid, hipStream_t st) {
   const int w = pow2_at_least((a.g + VEC - 1) / VEC);
   switch (w) {
-#define KVECC_ATTN_CASE(WW)                                                                       \
-  case WW:                                                                                        \
-    KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC, WW, BUF, 1>), grid, dim3(kBlock), 0, st, a); \
+#define KVECC_ATTN_CASE(WW)                \
+  case WW:                                 \
+    KVECC_SPLIT_LAUNCH(VEC, WW, BUF, 1);   \
     return KVECC_OK;
     KVECC_ATTN_CASE(1)
     KVECC_ATTN_CASE(2)
@@ -1413,8 +732,8 @@ static int launch_split_w(const AttnArgs &a, dim3 grid, hipStream_t st) {
   }
 }
 
-template <typename T, int CODEC, int VEC>
-static int launch_split(const AttnArgs &a, dim3 grid, hipStream_t st) {
+template <typename T, int CODEC, int VEC, typename A>
+static int launch_split(const A &a, dim3 grid, hipStream_t st) {
   return a.cache_bytes ? launch_split_w<T, CODEC, VEC, true>(a, grid, st)
                        : launch_split_w<T, CODEC, VEC, false>(a, grid, st);
 }
@@ -1441,18 +760,18 @@ static int attn_heads_per_wg(int codec, int64_t d, int64_t g, int64_t heads, int
   return group % 4 == 0 && gmax >= 4 ? 4 : group % 2 == 0 ? 2 : 1;
 }
 
-template <typename T, int CODEC, int VEC, int G>
-static int launch_split_gqa(const AttnArgs &a, dim3 grid, hipStream_t st) {
+template <typename T, int CODEC, int VEC, int G, typename A>
+static int launch_split_gqa(const A &a, dim3 grid, hipStream_t st) {
   switch (pow2_at_least((a.g + VEC - 1) / VEC)) {
-    case 8: KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC, 8, true, G>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC, 16, true, G>), grid, dim3(kBlock), 0, st, a); break;
-    default: KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC, 32, true, G>), grid, dim3(kBlock), 0, st, a); break;
+    case 8: KVECC_SPLIT_LAUNCH(VEC, 8, true, G); break;
+    case 16: KVECC_SPLIT_LAUNCH(VEC, 16, true, G); break;
+    default: KVECC_SPLIT_LAUNCH(VEC, 32, true, G); break;
   }
   return KVECC_OK;
 }
 
-template <typename T, int CODEC, int VEC>
-static int launch_split_g(const AttnArgs &a, int64_t batch, int gq, hipStream_t st) {
+template <typename T, int CODEC, int VEC, typename A>
+static int launch_split_g(const A &a, int64_t batch, int gq, hipStream_t st) {
   dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gq));
   if (gq == 1) return launch_split<T, CODEC, VEC>(a, grid, st);
   constexpr int GV = CODEC == KVECC_CODEC_H84 ? kH84GqaVec : VEC;
@@ -1461,8 +780,8 @@ static int launch_split_g(const AttnArgs &a, int64_t batch, int gq, hipStream_t 
   return launch_split_gqa<T, CODEC, GV, 2>(a, grid, st);
 }
 
-template <typename T, int CODEC>
-static int launch_attn(const AttnArgs &a, int64_t batch, int gq, hipStream_t st) {
+template <typename T, int CODEC, typename A>
+static int launch_attn(const A &a, int64_t batch, int gq, hipStream_t st, bool combine = true) {
   int rc;
   if constexpr (CODEC == KVECC_CODEC_H84) {
     if (a.d % (4 * kH84Vec) == 0)
@@ -1477,7 +796,7 @@ static int launch_attn(const AttnArgs &a, int64_t batch, int gq, hipStream_t st)
     rc = launch_split_g<T, CODEC, kGolayPackedVec>(a, batch, gq, st);  // 3 codewords per lane: 43 -> 15 of 16
   }
   if (rc != KVECC_OK) return rc;
-  if (!a.ctr) launch_combine<T>(a, batch, st);
+  if (!a.ctr && combine) launch_combine<T>(a, batch, st);
   return KVECC_OK;
 }
 
@@ -1544,13 +863,63 @@ static int attn_mfma_heads(int codec, int q_dtype, const void *query, int64_t d,
   return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
 }
 
-template <typename T>
-static int launch_codec(int codec, const AttnArgs &a, int64_t batch, int gq, hipStream_t st) {
+template <typename T, typename A>
+static int launch_codec(int codec, const A &a, int64_t batch, int gq, hipStream_t st, bool combine = true) {
   switch (codec) {
-    case KVECC_CODEC_H84: return launch_attn<T, KVECC_CODEC_H84>(a, batch, gq, st);
-    case KVECC_CODEC_GOLAY: return launch_attn<T, KVECC_CODEC_GOLAY>(a, batch, gq, st);
-    default: return launch_attn<T, KVECC_CODEC_GOLAY_PACKED>(a, batch, gq, st);
+    case KVECC_CODEC_H84: return launch_attn<T, KVECC_CODEC_H84>(a, batch, gq, st, combine);
+    case KVECC_CODEC_GOLAY: return launch_attn<T, KVECC_CODEC_GOLAY>(a, batch, gq, st, combine);
+    default: return launch_attn<T, KVECC_CODEC_GOLAY_PACKED>(a, batch, gq, st, combine);
   }
+}
+
+// The general path of a chunked call: the split kernels over the virtual batch
+// of `rows` = batch * q_len query rows (AttnArgs::q_len), in slices that fit
+// grid.y, then one combine over all rows.
+constexpr int64_t kMaxGridY = 65535;
+template <typename T>
+static int launch_codec_rows(int codec, ChunkArgs a, int64_t rows, int gq, hipStream_t st) {
+  const int64_t wg_per_row = a.heads / gq;
+  if (rows * wg_per_row <= kMaxGridY) return launch_codec<T>(codec, a, rows, gq, st);
+  const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
+  for (int64_t vb = 0; vb < rows; vb += per) {
+    a.vb0 = (uint32_t)vb;
+    const int rc = launch_codec<T>(codec, a, std::min(per, rows - vb), gq, st, false);
+    if (rc != KVECC_OK) return rc;
+  }
+  launch_combine<T>(a, rows, st);
+  return KVECC_OK;
+}
+
+// heads per column group of the matrix-core chunk kernels (0: the general
+// path): attn_mfma_heads' domain with every query row 16-byte aligned, Golay
+// MHA included -- a decoded row serves 16 query columns here, so its decode
+// cost is shared where the decode-step kernel spends it on one
+static int attn_chunk_mfma_heads(int codec, int q_dtype, const void *query, int64_t sb, int64_t st, int64_t sh,
+                                 int64_t d, int64_t heads, int64_t kv_heads, bool buf) {
+  const int64_t group = heads / kv_heads;
+  const bool h84 = codec == KVECC_CODEC_H84 && (d == 32 || d == 64 || d == 128);
+  const bool golay = (codec == KVECC_CODEC_GOLAY || codec == KVECC_CODEC_GOLAY_PACKED) && d == 128;
+  if (!(h84 || golay) || q_dtype != KVECC_F16 || !buf) return 0;
+  if (!aligned(query, 16) || sb % 8 || st % 8 || sh % 8) return 0;
+  if (group == 1) return 1;
+  return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
+}
+
+static int launch_mfma_chunk(int codec, const ChunkArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
+  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
+  if (codec == KVECC_CODEC_GOLAY_PACKED) {
+    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<true>), grid, dim3(kBlock), 0, st, a);
+  } else if (codec == KVECC_CODEC_GOLAY) {
+    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<false>), grid, dim3(kBlock), 0, st, a);
+  } else {
+    switch (a.d) {
+      case 32: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
+      case 64: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
+      default: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
+    }
+  }
+  launch_combine<__half>(a, batch * a.q_len, st);
+  return KVECC_OK;
 }
 
 // tokens per workgroup: the largest power of two <= kMaxSplit that still gives
@@ -1694,6 +1063,174 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
   }
   if (rc != KVECC_OK) return rc;
   return check_launch("paged_attention");
+}
+
+// ---- chunked causal attention ---------------------------------------------------
+// The finest split a chunked call can pick: its matrix-core grid has at least
+// rows / 16 workgroups per split (16 query rows per tile), the split kernels'
+// rows / 4.
+static int64_t chunk_finest_split(int64_t rows, int64_t max_context_len) {
+  return choose_split(std::max<int64_t>(1, rows / 16), max_context_len);
+}
+
+KVECC_API int64_t kvecc_paged_attention_chunk_workspace(int64_t batch, int64_t q_len, int64_t heads,
+                                                        int64_t head_dim, int64_t max_context_len) {
+  if (batch < 0 || q_len < 0 || heads < 0 || head_dim < 0) {
+    set_error(KVECC_EINVAL, "paged_attention_chunk_workspace: negative size");
+    return KVECC_EINVAL;
+  }
+  if (batch == 0 || q_len == 0 || heads == 0 || head_dim == 0 || max_context_len <= 0) return 0;
+  if (q_len == 1) return kvecc_paged_attention_workspace(batch, heads, head_dim, max_context_len);
+  const int64_t rows = batch * q_len * heads;
+  return rows * cdiv(max_context_len, chunk_finest_split(rows, max_context_len)) * (head_dim + 2);
+}
+
+KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_stride,
+                                          int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                          const void *k_cache, const void *v_cache,
+                                          const int32_t *block_table, const int32_t *context_lens,
+                                          const float *k_scales, const float *v_scales, void *out,
+                                          int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
+                                          int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                          int64_t layer, int64_t block_size, int64_t max_blocks,
+                                          int64_t max_context_len, float sm_scale, int codec,
+                                          float *workspace, int64_t workspace_floats, void *stream) {
+  if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
+  if (batch == 0 || q_len == 0 || heads == 0) return KVECC_OK;
+  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
+      (heads > 1 && q_head_stride < head_dim) || (q_len > 1 && q_token_stride < head_dim))
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: query strides (%lld, %lld, %lld) for head_dim %lld",
+                     (long long)q_batch_stride, (long long)q_token_stride, (long long)q_head_stride,
+                     (long long)head_dim);
+  // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
+  if (q_len == 1 && (heads == 1 || q_head_stride == head_dim) && (batch == 1 || q_batch_stride == heads * head_dim))
+    return kvecc_paged_attention(query, q_dtype, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, batch, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size,
+                                 max_blocks, max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
+  if (kv_heads < 1 || heads % kv_heads != 0)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld heads not a multiple of %lld kv heads",
+                     (long long)heads, (long long)kv_heads);
+  if (head_dim < 1 || head_dim > kAttnMaxD)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: head_dim %lld not in [1, %d]", (long long)head_dim,
+                     kAttnMaxD);
+  if (codec != KVECC_CODEC_H84 && codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: codec %d (hamming84 or golay only)", codec);
+  if (codec == KVECC_CODEC_H84 && head_dim % 4 != 0)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: hamming84 head_dim must be a multiple of 4");
+  if (q_dtype != KVECC_F32 && q_dtype != KVECC_F16 && q_dtype != KVECC_BF16)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: bad dtype %d", q_dtype);
+  if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: bad cache geometry");
+  if (num_blocks < 1 || num_blocks * num_layers * kv_heads * block_size > 0x7FFFFFFFLL)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: cache rows must fit int32");
+  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
+  if (!query || !k_cache || !v_cache || !block_table || !context_lens || !k_scales || !v_scales ||
+      !out || !workspace)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: null pointer");
+  const int64_t vbatch = batch * q_len;  // query rows per head: the virtual batch
+  if (q_len > 0x7FFFFFFFLL || vbatch > 0x7FFFFFFFLL || vbatch * heads > 0x7FFFFFFFLL)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld x %lld x %lld query rows exceed the grid",
+                     (long long)batch, (long long)q_len, (long long)heads);
+  const int64_t need = kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, max_context_len);
+  if (workspace_floats < need)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: workspace %lld < %lld floats",
+                     (long long)workspace_floats, (long long)need);
+  ChunkArgs a;
+  a.q = query;
+  a.k_cache = k_cache;
+  a.v_cache = v_cache;
+  a.table = block_table;
+  a.ctx_lens = context_lens;
+  a.k_scales = k_scales;
+  a.v_scales = v_scales;
+  a.ws = workspace;
+  a.out = out;
+  a.heads = heads;
+  a.kv_heads = kv_heads;
+  a.d = head_dim;
+  a.g = codec == KVECC_CODEC_H84 ? head_dim / 4 : (head_dim + 2) / 3;
+  a.rowb = (uint32_t)KVECC_GOLAY_PACKED_ROW(a.g);
+  a.layers = num_layers;
+  a.layer = layer;
+  a.bs = block_size;
+  a.max_blocks = max_blocks;
+  a.ctx_cap = std::min(max_context_len, max_blocks * block_size);
+  a.sm_scale = sm_scale;
+  a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
+  a.q_len = (uint32_t)q_len;
+  a.vb0 = 0;
+  a.q_sb = q_batch_stride;
+  a.q_st = q_token_stride;
+  a.q_sh = q_head_stride;
+  a.cg_log2 = 0;
+  int64_t tiles = 1;  // matrix-core chunk kernels: 16-column tiles per (sequence, head group)
+  const int64_t rows_total = num_blocks * num_layers * kv_heads * block_size;
+  const int64_t cb = rows_total * (codec == KVECC_CODEC_H84            ? head_dim
+                                   : codec == KVECC_CODEC_GOLAY_PACKED ? (int64_t)a.rowb
+                                                                       : 4 * a.g);
+  const bool fits = cb <= 0xFFFFFFFFLL && rows_total * 4 <= 0xFFFFFFFFLL;
+  a.cache_bytes = fits ? (uint32_t)cb : 0u;  // 0 selects the 64-bit-addressed kernels
+  a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
+  const int gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
+  // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound)
+  int gm = q_len > 1 ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
+                                             head_dim, heads, kv_heads, fits)
+                     : 0;
+  int64_t wgs = 0;  // workgroups per split
+  if (gm) {
+    for (a.cg_log2 = 0; (1 << a.cg_log2) < gm; ++a.cg_log2) {}
+    tiles = cdiv(q_len, 16 / gm);
+    wgs = batch * (heads / gm) * tiles;
+    if (batch * (heads / gm) > kMaxGridY) gm = 0;  // the split kernels slice their grid
+  }
+  if (!gm) {
+    a.cg_log2 = 0;
+    wgs = vbatch * heads / gq;
+    if (heads / gq > kMaxGridY)
+      return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld heads exceed the grid", (long long)heads);
+  }
+  const int64_t finest = q_len > 1 ? chunk_finest_split(vbatch * heads, max_context_len)
+                                   : choose_split(std::max<int64_t>(1, batch * heads / 4), max_context_len);
+  a.split = std::max(choose_split(wgs, max_context_len,
+                                  !gm                        ? 4
+                                  : codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu
+                                                             : kMfmaWgPerCu),
+                     finest);
+  a.nsplit = cdiv(max_context_len, a.split);
+  if (a.nsplit > kMaxSplits)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: context %lld too long", (long long)max_context_len);
+  if (gm && a.nsplit * tiles > 0x7FFFFFFFLL)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld splits x %lld tiles exceed the grid",
+                     (long long)a.nsplit, (long long)tiles);
+  a.par = a.cor = nullptr;
+  a.atab = a.atab_x = nullptr;
+  a.ctr = nullptr;
+  // the counted combine as in the decode entry: one query head per workgroup of the split kernels
+  if (!gm && gq == 1 && vbatch * heads <= kAttnCtrPerSlot) {
+    a.ctr = attn_counter_slot(stream);
+    if (!a.ctr) return KVECC_EHIP;
+  }
+  if (codec != KVECC_CODEC_H84) {
+    a.par = golay_parity_table_dev();
+    a.cor = golay_correct_table_dev();
+    a.atab = golay_attn_table_dev();
+    a.atab_x = golay_attn_x_table_dev();
+    if (!a.par || !a.cor || !a.atab || !a.atab_x) return KVECC_EHIP;
+  }
+  hipStream_t st = as_stream(stream);
+  int rc;
+  if (gm) {
+    rc = launch_mfma_chunk(codec, a, batch, tiles, st);
+  } else {
+    switch (q_dtype) {
+      case KVECC_F32: rc = launch_codec_rows<float>(codec, a, vbatch, gq, st); break;
+      case KVECC_F16: rc = launch_codec_rows<__half>(codec, a, vbatch, gq, st); break;
+      default: rc = launch_codec_rows<__hip_bfloat16>(codec, a, vbatch, gq, st); break;
+    }
+  }
+  if (rc != KVECC_OK) return rc;
+  return check_launch("paged_attention_chunk");
 }
 
 }  // extern "C"

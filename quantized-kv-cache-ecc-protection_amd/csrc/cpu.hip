@@ -860,17 +860,19 @@ KVECC_API int kvecc_cpu_shim_read_batch(const void *k_cache, const void *v_cache
 // softmax in fp32 (attention_ecc.py:355-427).  No valid token: Hamming(8,4)
 // -8.0 per lane (the reference kernel's -1e20 masking, :342,391-423), Golay 0
 // (reference_attention_ecc, :806-807,885-886).
-KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const void *k_cache,
-                                        const void *v_cache, const int32_t *block_table,
-                                        const int32_t *context_lens, const float *k_scales,
-                                        const float *v_scales, void *out, int64_t batch,
-                                        int64_t heads, int64_t kv_heads, int64_t head_dim,
-                                        int64_t num_blocks, int64_t num_layers, int64_t layer, int64_t block_size,
-                                        int64_t max_blocks, int64_t max_context_len,
-                                        float sm_scale, int codec, int threads) {
+// One body for both entries: query row (b, t, h) at b*q_sb + t*q_st + h*q_sh
+// (elements), at position context_lens[b] - q_len + t, attending to the keys at
+// or before it; q_len 1 is the decode entry.
+static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int64_t q_sh, int q_dtype,
+                              const void *k_cache, const void *v_cache, const int32_t *block_table,
+                              const int32_t *context_lens, const float *k_scales, const float *v_scales,
+                              void *out, int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
+                              int64_t head_dim, int64_t num_blocks, int64_t num_layers, int64_t layer,
+                              int64_t block_size, int64_t max_blocks, int64_t max_context_len,
+                              float sm_scale, int codec, int threads) {
   if (batch < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: negative size");
-  if (batch == 0 || heads == 0) return KVECC_OK;
+  if (batch == 0 || heads == 0 || q_len == 0) return KVECC_OK;
   if (kv_heads < 1 || heads % kv_heads != 0)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: heads not a multiple of kv heads");
   if (head_dim < 1) return set_error(KVECC_EINVAL, "cpu_paged_attention: empty head_dim");
@@ -894,7 +896,7 @@ KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const vo
   const bool golay = codec == KVECC_CODEC_GOLAY || packed;
   const int64_t g = golay ? (head_dim + 2) / 3 : head_dim;
   const int64_t groups = heads / kv_heads;
-  parallel_for(batch * heads, threads, 1, [&](int64_t b0, int64_t e0, int) {
+  parallel_for(batch * q_len * heads, threads, 1, [&](int64_t b0, int64_t e0, int) {
     std::vector<float> q(head_dim), kv(head_dim), acc(head_dim);
     auto decode_row = [&](const void *cache, int64_t srow, float s) {
       if (golay) {
@@ -920,11 +922,11 @@ KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const vo
       }
     };
     for (int64_t bh = b0; bh < e0; ++bh) {
-      const int64_t b = bh / heads, h = bh % heads, hk = h / groups;
-      for (int64_t j = 0; j < head_dim; ++j) q[j] = load_x(query, q_dtype, bh * head_dim + j);
+      const int64_t b = bh / (q_len * heads), t = bh / heads % q_len, h = bh % heads, hk = h / groups;
+      for (int64_t j = 0; j < head_dim; ++j) q[j] = load_x(query, q_dtype, b * q_sb + t * q_st + h * q_sh + j);
       std::fill(acc.begin(), acc.end(), 0.0f);
       float m = -INFINITY, l = 0.0f;
-      const int64_t ctx = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len),
+      const int64_t ctx = std::min<int64_t>(std::min<int64_t>((int64_t)context_lens[b] - q_len + 1 + t, max_context_len),
                                             max_blocks * block_size);
       for (int64_t pos = 0; pos < ctx; ++pos) {
         const int32_t blk = block_table[b * max_blocks + pos / block_size];
@@ -948,6 +950,41 @@ KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const vo
     }
   });
   return KVECC_OK;
+}
+
+KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const void *k_cache,
+                                        const void *v_cache, const int32_t *block_table,
+                                        const int32_t *context_lens, const float *k_scales,
+                                        const float *v_scales, void *out, int64_t batch,
+                                        int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                        int64_t num_blocks, int64_t num_layers, int64_t layer, int64_t block_size,
+                                        int64_t max_blocks, int64_t max_context_len,
+                                        float sm_scale, int codec, int threads) {
+  return cpu_attention_impl(query, heads * head_dim, 0, head_dim, q_dtype, k_cache, v_cache, block_table,
+                            context_lens, k_scales, v_scales, out, batch, 1, heads, kv_heads, head_dim,
+                            num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale,
+                            codec, threads);
+}
+
+// Chunked causal twin (kvecc_paged_attention_chunk): the same decode and fp32
+// online softmax per (b, t, h) row, out [batch, q_len, heads, head_dim].
+KVECC_API int kvecc_cpu_paged_attention_chunk(const void *query, int64_t q_batch_stride,
+                                              int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                              const void *k_cache, const void *v_cache,
+                                              const int32_t *block_table, const int32_t *context_lens,
+                                              const float *k_scales, const float *v_scales, void *out,
+                                              int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
+                                              int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                              int64_t layer, int64_t block_size, int64_t max_blocks,
+                                              int64_t max_context_len, float sm_scale, int codec, int threads) {
+  if (q_len < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk: negative q_len");
+  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
+      (heads > 1 && q_head_stride < head_dim) || (q_len > 1 && q_token_stride < head_dim))
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk: bad query strides");
+  return cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                            block_table, context_lens, k_scales, v_scales, out, batch, q_len, heads, kv_heads,
+                            head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
+                            sm_scale, codec, threads);
 }
 
 }  // extern "C"

@@ -68,6 +68,10 @@ SIGNATURES = {
     "kvecc_paged_attention_workspace": [_i64, _i64, _i64, _i64],
     "kvecc_paged_attention": [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
                               _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp, _i64, _vp],
+    "kvecc_paged_attention_chunk_workspace": [_i64, _i64, _i64, _i64, _i64],
+    "kvecc_paged_attention_chunk": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                    _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp, _i64,
+                                    _vp],
     # host backend (threads instead of a stream)
     "kvecc_cpu_hamming74_encode": [_vp, _vp, _i64, _int],
     "kvecc_cpu_hamming84_encode": [_vp, _vp, _i64, _int],
@@ -98,12 +102,16 @@ SIGNATURES = {
                                   _int, _vp, _vp, _int, _vp, _int],
     "kvecc_cpu_paged_attention": [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
                                   _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int],
+    "kvecc_cpu_paged_attention_chunk": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
+                                        _int],
 }
 _RESTYPE = {
     "kvecc_version": ctypes.c_char_p,
     "kvecc_last_error": ctypes.c_char_p,
     "kvecc_ber_threshold": ctypes.c_uint32,
     "kvecc_paged_attention_workspace": ctypes.c_int64,
+    "kvecc_paged_attention_chunk_workspace": ctypes.c_int64,
 }
 
 # dtype / codec codes (include/kvecc.h)

@@ -576,6 +576,24 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
     return out
 
 
+def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
+    """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
+    from .ops import _check_attention_chunk_args
+    _check_cpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    batch, q_len, heads, head_dim = query.shape
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    max_blocks = block_table.shape[1]
+    _lib.call("kvecc_cpu_paged_attention_chunk", _ptr(query), query.stride(0), query.stride(1),
+              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+              _ptr(context_lens), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads,
+              head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+              int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
+    return out
+
+
 def paged_attention_ecc(query, k_cache, v_cache, block_table, context_lens, k_scales, layer_idx,
                         block_size, sm_scale=None, codec="hamming84", syndrome_table=None,
                         use_tiled=False, block_m=4, v_scales=None):

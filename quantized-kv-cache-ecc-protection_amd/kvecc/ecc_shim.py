@@ -105,7 +105,18 @@ class ECCShimConfig:
     generates token by token.  "append" needs a fused codec (int4, hamming74,
     hamming84, golay) and fused=True.  ``decode_stats`` (append mode) sends
     single-token steps through the counting read instead of the paged
-    attention kernels, which keep no statistics.
+    attention kernels, which keep no statistics.  ``chunk_attention`` (append
+    mode, opt-in) sends the forwards of more than one token -- the prefill, a
+    chunk of it, the draft tokens of a verify step -- through the chunked
+    causal paged attention kernel (kvecc_paged_attention_chunk) instead of the
+    batched read + masked SDPA, under the decode step's conditions (hamming84
+    or golay, no interpolation, decode_stats off, head_dim <= 256).  Like the
+    decode step it keeps no decode statistics, which the default prefill does
+    count: that is why it is off by default.  It was faster than the default
+    path in every case measured (fp16, head_dim 128, 4- and 16-token chunks,
+    MHA and 4 query heads per cache head: profiles/chunk_attention/); fp32 and
+    bf16 models and other head_dims run the split kernels once per query row,
+    which re-decode the cache for each and have not been measured.
     """
 
     SUPPORTED_CODECS = {"fp16", "fp8", "int4", "hamming74", "hamming84", "golay"}
@@ -114,7 +125,7 @@ class ECCShimConfig:
     def __init__(self, codec="hamming84", ber=0.0, block_size=16, num_blocks=256,
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
-                 decode_stats=False):
+                 decode_stats=False, chunk_attention=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -140,6 +151,9 @@ class ECCShimConfig:
                              f"not codec={codec!r}, fused={fused}")
         self.cache_mode = cache_mode
         self.decode_stats = decode_stats
+        if chunk_attention and cache_mode != "append":
+            raise ValueError("chunk_attention=True needs cache_mode='append'")
+        self.chunk_attention = bool(chunk_attention)
 
 
 class SimpleBlockManager:
@@ -474,6 +488,22 @@ class ECCBackend:
                 q1, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx)
             return out.unsqueeze(2)
+        if q_len > 1 and cfg.chunk_attention and cfg.codec in ("hamming84", "golay") and not interp \
+                and not cfg.decode_stats and d <= 256:
+            # prefill / chunk / verify step on the chunked causal kernel: q read
+            # in place as [batch, q_len, heads, d], no dense K / V, no statistics
+            qt = q.transpose(1, 2)
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention_chunk(qt, mgr.k_cache, mgr.v_cache, table, dev_lens,
+                                                            mgr.k_scales, mgr.v_scales, layer_idx,
+                                                            mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec,
+                                                            ctx)
+                return out.transpose(1, 2)
+            out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+            self.codec_backend.paged_attention_chunk_into(
+                qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx)
+            return out.transpose(1, 2)
         # prefill, chunks, hamming74 / int4, interpolation, decode_stats: one
         # batched read at the longest length, then masked SDPA.  The read
         # decodes ctx rows of every sequence: a shorter sequence's rows past

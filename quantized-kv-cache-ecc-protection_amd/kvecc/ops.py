@@ -929,6 +929,42 @@ def _check_attention_args(query, k_cache, v_cache, block_table, context_lens, k_
             raise ValueError(f"{name} must be contiguous")
 
 
+def _check_attention_rest(batch, heads, head_dim, device, k_cache, v_cache, block_table, context_lens,
+                          k_scales, v_scales, block_size, codec):
+    """The chunked entry's checks of everything but the query and out, as
+    _check_attention_args makes them for the decode entry: cache dtypes and
+    geometry against the codec and block_size, table and lengths against the
+    batch, one device, contiguity."""
+    if codec not in _ATTN_CACHE_DT:
+        raise ValueError(f"paged attention codec {codec!r} (hamming84, golay or golay_packed)")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
+    nb, nl, kvh, row = k_cache.shape
+    per = _ATTN_ROW_WORDS[codec](head_dim)
+    for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if c.dtype != _ATTN_CACHE_DT[codec]:
+            raise ValueError(f"{codec} {name} must be {_ATTN_CACHE_DT[codec]}, got {c.dtype}")
+    if row != block_size * per:
+        raise ValueError(f"{codec} cache rows hold {row} words, expected block_size*{per} = "
+                         f"{block_size * per}")
+    if kvh < 1 or heads % kvh:
+        raise ValueError(f"{heads} query heads not a multiple of {kvh} kv heads")
+    if block_table.dim() != 2 or block_table.shape[0] != batch or block_table.dtype != torch.int32:
+        raise ValueError("block_table must be int32 [B, max_blocks]")
+    if context_lens.shape != (batch,) or context_lens.dtype != torch.int32:
+        raise ValueError("context_lens must be int32 [B]")
+    for name, sc in (("k_scales", k_scales), ("v_scales", v_scales)):
+        if sc.shape != (nb, nl, kvh, block_size) or sc.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 [{nb}, {nl}, {kvh}, {block_size}], got "
+                             f"{tuple(sc.shape)} {sc.dtype}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache), ("block_table", block_table),
+                    ("context_lens", context_lens), ("k_scales", k_scales), ("v_scales", v_scales)):
+        if t.device != device:
+            raise ValueError(f"{name} is on {t.device}, query on {device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+
 def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                          out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
     """kvecc_paged_attention on [B, H, D] query / out (see include/kvecc.h).
@@ -955,6 +991,71 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
               max_blocks, mcl, float(sm_scale), SHIM_CODECS[codec], _ptr(ws), ws.numel(),
               _stream(query.device))
     return out
+
+
+def _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec):
+    """_check_attention_args for a [B, q_len, H, D] query of any strides with a
+    unit innermost one and a contiguous out of the same shape and dtype."""
+    if query.dim() != 4 or query.dtype not in _DT:
+        raise ValueError(f"query must be [B, q_len, H, D] fp32/fp16/bf16, got {tuple(query.shape)} {query.dtype}")
+    batch, q_len, heads, head_dim = query.shape
+    if head_dim > 1 and query.stride(3) != 1:
+        raise ValueError(f"query's innermost stride must be 1, got {query.stride(3)}")
+    if (heads > 1 and query.stride(2) < head_dim) or (q_len > 1 and query.stride(1) < head_dim):
+        raise ValueError(f"query strides {query.stride()} overlap its head_dim {head_dim} rows")
+    if out.shape != query.shape or out.dtype != query.dtype:
+        raise ValueError(f"out must be query's [B, q_len, H, D] {query.dtype}, got {tuple(out.shape)} {out.dtype}")
+    if query.device != out.device:
+        raise ValueError(f"query is on {query.device}, out on {out.device}")
+    _check_attention_rest(batch, heads, head_dim, query.device, k_cache, v_cache, block_table, context_lens,
+                          k_scales, v_scales, block_size, codec)
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+
+
+def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
+    """kvecc_paged_attention_chunk: q_len query tokens per sequence, causal (include/kvecc.h).
+
+    query [B, q_len, H, D] with any strides and a unit innermost one (the
+    [B, H, q_len, D] tensor transposed, or a [B, q_len, H*D] projection viewed,
+    are read in place); out contiguous [B, q_len, H, D] in the query's dtype.
+    context_lens counts the chunk's own tokens: query t sits at position
+    context_lens[b] - q_len + t.  Arguments are validated as in
+    paged_attention_into and the same cached workspace is used."""
+    _check_gpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    batch, q_len, heads, head_dim = query.shape
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    max_blocks = block_table.shape[1]
+    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
+    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
+    ws = _attn_workspace(query.device, ws_n)
+    _lib.call("kvecc_paged_attention_chunk", _ptr(query), query.stride(0), query.stride(1), query.stride(2),
+              _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table), _ptr(context_lens),
+              _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads, head_dim, num_blocks,
+              num_layers, int(layer_idx), int(block_size), max_blocks, mcl, float(sm_scale),
+              SHIM_CODECS[codec], _ptr(ws), ws.numel(), _stream(query.device))
+    return out
+
+
+def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                          layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0):
+    """paged_attention_chunk_into with a fresh [B, q_len, H, D] output; on the
+    GPU or, for host tensors, through the host twin."""
+    if sm_scale is None:
+        sm_scale = 1.0 / math.sqrt(query.shape[-1])
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    if query.device.type == "cpu":
+        from . import cpu_ops
+        return cpu_ops.paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
+                                                  v_scales, out, layer_idx, block_size, sm_scale, codec,
+                                                  max_context_len=max_context_len)
+    return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                      out, layer_idx, block_size, sm_scale, codec,
+                                      max_context_len=max_context_len)
 
 
 def _conform(t, dtype):

@@ -4,6 +4,13 @@ One decode step of [B, H, D] queries over a paged Hamming(8,4) (or Golay) KV
 cache of `ctx` tokens per sequence (BASELINE's [8, 4096, 32, 128] shape by
 default).  Algorithmic bytes per launch = K + V codewords + K/V scales + the
 block table; reported against the 8 TB/s HBM peak.  Prints one JSON line.
+
+--q-len N (N > 1) times a chunk of N query tokens per sequence (the last N of
+the context) three ways at the same shape and data, and prints all three: the
+chunked causal kernel (paged_attention_chunk_into), N decode calls (one per
+chunk token, at its own context length), and the path the shim takes without
+chunk_attention, composed as ECCBackend._append_attend composes it:
+shim_read_batch + repeat_interleave + the causal mask + SDPA.
 """
 
 from __future__ import annotations
@@ -41,6 +48,7 @@ def main():
                          "correction path: the decode tables' worst case), or encoded random INT4 values with "
                          "bit errors at --ber (what a cache holds)")
     ap.add_argument("--ber", type=float, default=None, help="encoded data: BER (default 1e-3 H84, 1e-2 Golay)")
+    ap.add_argument("--q-len", type=int, default=1, help="query tokens per sequence (1: one decode step)")
     args = ap.parse_args()
     from kvecc import ops
     dev = torch.device("cuda:0")
@@ -86,33 +94,79 @@ def main():
                                             1 / math.sqrt(args.d), args.codec, args.ctx)
     import statistics
     import time
-    t0 = time.perf_counter()
-    while True:
-        for _ in range(args.warmup):
-            call()
-        torch.cuda.synchronize()
-        if time.perf_counter() - t0 >= args.warmup_s:
-            break
-    passes = []
-    for _ in range(args.passes):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        passes.append(e0.elapsed_time(e1) / args.iters)
-    ms = statistics.median(passes)
+
+    def timed(fn):
+        """-> (median ms per call, the passes' ms per call) after the warm-up."""
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 >= args.warmup_s:
+                break
+        passes = []
+        for _ in range(args.passes):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            passes.append(e0.elapsed_time(e1) / args.iters)
+        return statistics.median(passes), passes
+
     tokens = args.batch * args.ctx
     cw_bytes = 2 * tokens * args.kv_heads * per * kc.element_size()
     bytes_ = cw_bytes + 2 * tokens * args.kv_heads * 4 + table.numel() * 4
+    data = args.data if args.data == "random" else f"encoded, BER {ber}"
+    if args.q_len > 1:
+        import torch.nn.functional as F
+        n, groups, sm = args.q_len, args.heads // args.kv_heads, 1 / math.sqrt(args.d)
+        qc = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half()  # the shim's layout
+        qt = qc.transpose(1, 2)
+        outc = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+        q1 = [qc[:, :, t].contiguous() for t in range(n)]
+        lens1 = [lens - (n - 1 - t) for t in range(n)]
+        stats = ops.new_stats(dev)
+
+        def chunk():
+            ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm, args.codec,
+                                           args.ctx)
+
+        def decodes():
+            for t in range(n):
+                ops.paged_attention_into(q1[t], kc, vc, table, lens1[t], ks, vs, out, 0, args.bs, sm, args.codec,
+                                         args.ctx)
+
+        def read_sdpa():
+            k_t, v_t = ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, args.codec, qc.dtype,
+                                           stats=stats, interp=False)
+            if groups > 1:
+                k_t = k_t.repeat_interleave(groups, dim=1)
+                v_t = v_t.repeat_interleave(groups, dim=1)
+            qpos = (lens - n).view(-1, 1, 1) + torch.arange(n, device=dev).view(1, n, 1)
+            mask = torch.arange(args.ctx, device=dev).view(1, 1, args.ctx) <= qpos
+            return F.scaled_dot_product_attention(qc, k_t, v_t, attn_mask=mask.unsqueeze(1))
+
+        res = {}
+        for name, fn in (("chunk", chunk), ("decode_calls", decodes), ("read_sdpa", read_sdpa)):
+            ms, passes = timed(fn)
+            res[name] = {"ms_per_call": ms, "pass_ms": [round(x, 5) for x in passes],
+                         "spread_ms": max(passes) - min(passes)}
+        gbs = bytes_ / (res["chunk"]["ms_per_call"] * 1e-3) / 1e9
+        print(json.dumps({"kernel": "paged_attention_chunk", "codec": args.codec, "batch": args.batch,
+                          "q_len": n, "heads": args.heads, "kv_heads": args.kv_heads, "head_dim": args.d,
+                          "ctx": args.ctx, **res, "bytes_per_call": bytes_, "chunk_achieved_gbs": gbs,
+                          "chunk_hbm_frac": gbs / 8000.0, "data": data}))
+        return
+    ms, passes = timed(call)
     gbs = bytes_ / (ms * 1e-3) / 1e9
     print(json.dumps({"kernel": "paged_attention", "codec": args.codec, "batch": args.batch,
                       "heads": args.heads, "kv_heads": args.kv_heads, "head_dim": args.d,
                       "ctx": args.ctx, "ms_per_call": ms, "bytes_per_call": bytes_,
                       "pass_ms": [round(x, 5) for x in passes],
                       "achieved_gbs": gbs, "hbm_frac": gbs / 8000.0,
-                      "data": args.data if args.data == "random" else f"encoded, BER {ber}",
+                      "data": data,
                       "includes": "split kernel + combine kernel + workspace alloc"}))
 
 
