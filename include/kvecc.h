@@ -348,6 +348,38 @@ KVECC_API int kvecc_shim_append(const void *k, const void *v, int64_t k_batch_st
                                 const int32_t *block_table, int64_t table_stride,
                                 const int32_t *start_pos, int64_t num_layers,
                                 int64_t block_size, int64_t layer, void *stream);
+/* Query spans (ragged batches; no reference counterpart).  A ragged call keeps
+ * the rectangular [batch, q_max, ...] tensors and adds q_spans, an int32
+ * [batch, 3] of (first, count, row_base) per sequence: token t of row b is
+ * VALID iff first >= 0 and first <= t < min(first + count, q_max), else
+ * PADDING (left padding: first = q_max - count; right padding: first = 0; an
+ * inactive sequence: count = 0; a full row: (0, q_max)).  A span that overruns
+ * q_max is clamped and never read past; a negative first or a count <= 0 makes
+ * the whole row padding.  row_base is the exclusive prefix sum of the valid
+ * counts before b; only the append reads it.  On the device entries q_spans is
+ * a DEVICE pointer the host never reads, on the kvecc_cpu_ twins a host one;
+ * null is KVECC_EINVAL.
+ *
+ * kvecc_shim_append with spans: the arguments are kvecc_shim_append's with
+ * q_len read as q_max.  Valid token t of sequence b goes to logical position
+ * start_pos[b] + (t - first); a padding token writes nothing (no cache byte,
+ * no scale) and its K/V elements are never loaded.  The injection row is dense
+ * over the valid tokens, r = (row_base + t - first)*hkv + h (K seed0 + r, V
+ * seed0 + r + 1); kvecc_shim_append's skip rules apply to valid tokens, which
+ * keep their r.  All spans (0, q_max, b*q_max) write kvecc_shim_append's bits;
+ * sequence b of any call holds what a batch-1 kvecc_shim_append of its valid
+ * tokens writes with seed0 + row_base*hkv. */
+KVECC_API int kvecc_shim_append_ragged(const void *k, const void *v, int64_t k_batch_stride,
+                                       int64_t k_seq_stride, int64_t k_head_stride,
+                                       int64_t v_batch_stride, int64_t v_seq_stride,
+                                       int64_t v_head_stride, int x_dtype, int64_t batch, int64_t q_max,
+                                       int64_t hkv, int64_t d, int codec, int scale_rule, int n_bits,
+                                       int inject, float ber, int64_t seed0, void *k_cache,
+                                       void *v_cache, float *k_scales, float *v_scales,
+                                       const int32_t *block_table, int64_t table_stride,
+                                       const int32_t *start_pos, const int32_t *q_spans,
+                                       int64_t num_layers, int64_t block_size, int64_t layer,
+                                       void *stream);
 /* ecc_shim.py:990-1071 (ECCBackend.attend, decode side) in ONE launch: gather
  * the first ctx tokens of layer `layer`, decode (H74: stats[0] += #flagged;
  * H84: stats[0] += #SINGLE_CORRECTED, stats[1] += #DOUBLE_DETECTED; Golay:
@@ -430,6 +462,29 @@ KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_str
                                           int64_t layer, int64_t block_size, int64_t max_blocks,
                                           int64_t max_context_len, float sm_scale, int codec,
                                           float *workspace, int64_t workspace_floats, void *stream);
+/* kvecc_paged_attention_chunk over query spans (see "Query spans" above): the
+ * arguments are that entry's with q_len read as q_max, plus q_spans after
+ * context_lens; the workspace is kvecc_paged_attention_chunk_workspace at
+ * q_len = q_max.  context_lens[b] counts sequence b's own valid tokens: valid
+ * token t sits at p = context_lens[b] - count + (t - first) and attends as a
+ * chunk row at p does.  A padding row gets the empty value (-8.0 for H84, 0
+ * for Golay) in every lane, and its query elements are never read, so NaN or
+ * Inf there reaches no output.  Launch geometry is chosen from batch, q_max and
+ * heads as the uniform entry chooses it: all spans (0, q_max, .) return that
+ * entry's bits for q_max > 1.  q_max 1 runs the split kernels (the decode
+ * entry knows no spans).  A workgroup whose query rows are all padding reads no
+ * table and no cache. */
+KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_batch_stride,
+                                                 int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                                 const void *k_cache, const void *v_cache,
+                                                 const int32_t *block_table, const int32_t *context_lens,
+                                                 const int32_t *q_spans, const float *k_scales,
+                                                 const float *v_scales, void *out, int64_t batch,
+                                                 int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                 int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                 int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                 int64_t max_context_len, float sm_scale, int codec,
+                                                 float *workspace, int64_t workspace_floats, void *stream);
 
 /* ---- Host ("cpu") backend ------------------------------------------------- */
 /* The reference has no CPU codec backend (every wrapper asserts x.is_cuda,
@@ -506,6 +561,15 @@ KVECC_API int kvecc_cpu_shim_append(const void *k, const void *v, int x_dtype, i
                                     int64_t table_stride, const int32_t *start_pos,
                                     int64_t num_layers, int64_t block_size, int64_t layer,
                                     int threads);
+/* kvecc_shim_append_ragged on contiguous K/V [batch, q_max, hkv*d]; start_pos and q_spans are host int32 */
+KVECC_API int kvecc_cpu_shim_append_ragged(const void *k, const void *v, int x_dtype, int64_t batch,
+                                           int64_t q_max, int64_t hkv, int64_t d, int codec,
+                                           int scale_rule, int n_bits, int inject, float ber,
+                                           int64_t seed0, void *k_cache, void *v_cache, float *k_scales,
+                                           float *v_scales, const int32_t *block_table,
+                                           int64_t table_stride, const int32_t *start_pos,
+                                           const int32_t *q_spans, int64_t num_layers,
+                                           int64_t block_size, int64_t layer, int threads);
 KVECC_API int kvecc_cpu_shim_read(const void *k_cache, const void *v_cache, const float *k_scales,
                                   const float *v_scales, const int32_t *block_table, int64_t ctx,
                                   int64_t hkv, int64_t d, int64_t num_layers, int64_t block_size,
@@ -535,6 +599,17 @@ KVECC_API int kvecc_cpu_paged_attention_chunk(const void *query, int64_t q_batch
                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
                                               int64_t layer, int64_t block_size, int64_t max_blocks,
                                               int64_t max_context_len, float sm_scale, int codec, int threads);
+KVECC_API int kvecc_cpu_paged_attention_chunk_ragged(const void *query, int64_t q_batch_stride,
+                                                     int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                                     const void *k_cache, const void *v_cache,
+                                                     const int32_t *block_table, const int32_t *context_lens,
+                                                     const int32_t *q_spans, const float *k_scales,
+                                                     const float *v_scales, void *out, int64_t batch,
+                                                     int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                     int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                     int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                     int64_t max_context_len, float sm_scale, int codec,
+                                                     int threads);
 
 #ifdef __cplusplus
 }

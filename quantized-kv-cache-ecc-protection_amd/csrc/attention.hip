@@ -125,8 +125,40 @@ struct ChunkArgs : AttnArgs {
   uint32_t cg_log2;          // matrix-core chunk kernels: log2 of the query heads per column group
   int64_t q_sb, q_st, q_sh;  // query strides in elements: batch, token, head
 };
+// Ragged calls (kvecc_paged_attention_chunk_ragged) add the spans behind
+// ChunkArgs, for the same reason: the uniform matrix-core chunk kernels keep
+// ChunkArgs and their code (with the field in ChunkArgs and the span rule in
+// their ChunkMap they measured 0.7-1.4 us slower per uniform call at
+// [8,4096,*,128], q_len 16, at unchanged registers and LDS:
+// profiles/ragged_attention), and the ragged entry runs matrix-core kernels of
+// its own names over the same bodies.  The split chunk kernels take RaggedArgs
+// for both entries.
+struct RaggedArgs : ChunkArgs {
+  // [batch, 3] (first, count, row_base) per sequence, q_len the rectangle's
+  // q_max; null: the uniform call, first = 0 and count = q_len
+  const int32_t *q_spans;
+};
+// A sequence's span: token t is valid iff first >= 0 and first <= t < min(first
+// + count, q_len), and sits at position ctx_lens[b] - count + (t - first).
+struct ChunkSpan {
+  int64_t first, count;
+  __device__ __forceinline__ ChunkSpan(const RaggedArgs &a, int64_t b) {
+    first = a.q_spans ? a.q_spans[3 * b] : 0;
+    count = a.q_spans ? a.q_spans[3 * b + 1] : a.q_len;
+  }
+  // [v0, v1): the valid tokens, empty when v1 <= v0
+  __device__ __forceinline__ int64_t v0() const { return first; }
+  __device__ __forceinline__ int64_t v1(const ChunkArgs &a) const {
+    return first < 0 ? first : min<int64_t>(first + count, a.q_len);
+  }
+  __device__ __forceinline__ bool valid(const ChunkArgs &a, int64_t t) const { return t >= first && t < v1(a); }
+  // token 0's key limit; token t's is that + t
+  __device__ __forceinline__ int64_t lim0(const ChunkArgs &a, int64_t b) const {
+    return (int64_t)a.ctx_lens[b] - count + 1 - first;
+  }
+};
 template <typename A>
-constexpr bool is_chunk = std::is_same<A, ChunkArgs>::value;
+constexpr bool is_chunk = std::is_base_of<ChunkArgs, A>::value;
 
 // Lane chunk c of a token row: VEC 32-bit words = 4*VEC H(8,4) codewords, or
 // VEC Golay codewords (3*VEC values; codewords past the row's last are read
@@ -506,7 +538,7 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_kernel(AttnArgs a) {
 }
 // the general path of a chunked call: the same body over the virtual batch (ChunkArgs)
 template <typename T, int CODEC, int VEC, int W, bool BUF, int G = 1>
-__global__ __launch_bounds__(kBlock) void paged_attn_split_chunk_kernel(ChunkArgs a) {
+__global__ __launch_bounds__(kBlock) void paged_attn_split_chunk_kernel(RaggedArgs a) {
   constexpr int UR = 0, DEC = 0;
 #define ATTN_BODY_CHUNK 1
 #include "attn_split_body.inc"
@@ -595,18 +627,25 @@ __device__ __forceinline__ void load_chunk(__amdgpu_buffer_rsrc_t rs, uint32_t o
 // context.  The chunk kernels use all 16 columns: with cg = 2^cg_log2 query
 // heads sharing the cache head, column n is chunk token tq = (16 / cg) tile +
 // n / cg and head h0 + n % cg, blockIdx.x = tile * nsplit + split.  Token tq
-// sits at position context_len - q_len + tq and sees the keys at or before it:
+// of a span (first, count) -- (0, q_len) in a uniform call -- is a query row when
+// the span holds it (ChunkSpan); it sits at position context_len - count + (tq -
+// first) and sees the keys at or before it:
 // its key limit is that position + 1, clamped to [0, ctx_cap]; the workgroup
-// walks the split up to the tile's largest limit (its last token's), each lane
-// masks the scores at or past its own column's.  A masked score is -inf like a
+// walks the split up to the tile's largest limit (its last valid token's), each
+// lane masks the scores at or past its own column's.  A padding column loads no
+// query and has limit 0.  A tile without a valid token (`any` false) stages
+// nothing: its workgroups write the empty partial (put_empty) and leave.  A masked score is -inf like a
 // -1 block's, so it has no weight in l, psum (the -8 fold) or the accumulators,
 // and a column with nothing to see in this split leaves m = -inf, l = 0.
-struct ChunkMap {
+template <typename A>
+struct ChunkMapT {
+  static constexpr bool kRagged = std::is_same<A, RaggedArgs>::value;
   int64_t b, h0, ctx;
   uint32_t split_idx, tile, tq, hq;
-  bool col_ok;  // the column holds a query row
+  bool col_ok;  // the column holds a query row (a valid token)
+  bool any;     // some column of the tile does
   int64_t lim;  // this column's key limit (absolute)
-  __device__ __forceinline__ ChunkMap(const ChunkArgs &a, int n) {
+  __device__ __forceinline__ ChunkMapT(const A &a, int n) {
     const uint32_t hgroups = (uint32_t)a.heads >> a.cg_log2;
     b = blockIdx.y / hgroups;
     h0 = (int64_t)(blockIdx.y % hgroups) << a.cg_log2;
@@ -615,11 +654,34 @@ struct ChunkMap {
     const uint32_t tpt = 16u >> a.cg_log2;  // tokens per tile
     tq = tile * tpt + ((uint32_t)n >> a.cg_log2);
     hq = (uint32_t)h0 + ((uint32_t)n & ((1u << a.cg_log2) - 1u));
-    col_ok = tq < a.q_len;
-    const int64_t first = (int64_t)a.ctx_lens[b] - a.q_len + 1;  // token 0's key limit
-    const uint32_t tlast = min(tile * tpt + tpt - 1u, a.q_len - 1u);
-    ctx = min<int64_t>(first + tlast, a.ctx_cap);
-    lim = col_ok ? min<int64_t>(first + tq, a.ctx_cap) : 0;
+    if constexpr (kRagged) {
+      const ChunkSpan sp(a, b);
+      col_ok = sp.valid(a, tq);
+      // the tile's valid tokens: [max(v0, tile start), min(v1, tile end))
+      const int64_t tv0 = max<int64_t>(sp.v0(), (int64_t)tile * tpt);
+      const int64_t tv1 = min<int64_t>(sp.v1(a), (int64_t)tile * tpt + tpt);
+      any = tv1 > tv0;
+      const int64_t first = any ? sp.lim0(a, b) : 0;  // token 0's key limit (no context_lens read without a token)
+      ctx = any ? min<int64_t>(first + tv1 - 1, a.ctx_cap) : 0;
+      lim = col_ok ? min<int64_t>(first + tq, a.ctx_cap) : 0;
+    } else {  // the uniform call: every token of the chunk is a query row
+      any = true;
+      col_ok = tq < a.q_len;
+      const int64_t first = (int64_t)a.ctx_lens[b] - a.q_len + 1;  // token 0's key limit
+      const uint32_t tlast = min(tile * tpt + tpt - 1u, a.q_len - 1u);
+      ctx = min<int64_t>(first + tlast, a.ctx_cap);
+      lim = col_ok ? min<int64_t>(first + tq, a.ctx_cap) : 0;
+    }
+  }
+  // a tile without a valid token: m = -inf, l = 0 and zero accumulators for
+  // every row of the tile in this split, which the combine turns into the empty value
+  __device__ __forceinline__ void put_empty(const ChunkArgs &a) const {
+    const int64_t stride = a.d + 2;
+    for (int64_t idx = threadIdx.x; idx < 16 * stride; idx += kBlock) {
+      const int h = (int)(idx / stride), e = (int)(idx - h * stride);
+      const int64_t orow = out_row(a, h);
+      if (orow >= 0) ws_put(a.ws + (orow * a.nsplit + split_idx) * stride + e, e == 0 ? -INFINITY : 0.0f);
+    }
   }
   // the column's limit relative to the split's first token t0, as an int the
   // lanes compare token indices against (clamped: a split has <= kMaxSplit tokens)
@@ -647,6 +709,16 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_kernel(AttnArgs
 template <int D>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_chunk_kernel(ChunkArgs a) {
   constexpr int G = 16;
+  using ChunkMap = ChunkMapT<ChunkArgs>;
+#define ATTN_BODY_CHUNK 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+// the ragged entry's: the same body with the span rule in its ChunkMap
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_ragged_kernel(RaggedArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
 #define ATTN_BODY_CHUNK 1
 #include "attn_h84_mfma_body.inc"
 #undef ATTN_BODY_CHUNK
@@ -681,6 +753,15 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_kernel(AttnAr
 template <bool PACKED>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_chunk_kernel(ChunkArgs a) {
   constexpr int G = 16;
+  using ChunkMap = ChunkMapT<ChunkArgs>;
+#define ATTN_BODY_CHUNK 1
+#include "attn_golay_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <bool PACKED>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_ragged_kernel(RaggedArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
 #define ATTN_BODY_CHUNK 1
 #include "attn_golay_mfma_body.inc"
 #undef ATTN_BODY_CHUNK
@@ -877,7 +958,7 @@ static int launch_codec(int codec, const A &a, int64_t batch, int gq, hipStream_
 // grid.y, then one combine over all rows.
 constexpr int64_t kMaxGridY = 65535;
 template <typename T>
-static int launch_codec_rows(int codec, ChunkArgs a, int64_t rows, int gq, hipStream_t st) {
+static int launch_codec_rows(int codec, RaggedArgs a, int64_t rows, int gq, hipStream_t st) {
   const int64_t wg_per_row = a.heads / gq;
   if (rows * wg_per_row <= kMaxGridY) return launch_codec<T>(codec, a, rows, gq, st);
   const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
@@ -905,17 +986,33 @@ static int attn_chunk_mfma_heads(int codec, int q_dtype, const void *query, int6
   return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
 }
 
-static int launch_mfma_chunk(int codec, const ChunkArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
+static int launch_mfma_chunk(int codec, const RaggedArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
   const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
+  if (a.q_spans) {  // the ragged entry's kernels
+    if (codec == KVECC_CODEC_GOLAY_PACKED) {
+      KVECC_LAUNCH((paged_attn_golay_mfma_ragged_kernel<true>), grid, dim3(kBlock), 0, st, a);
+    } else if (codec == KVECC_CODEC_GOLAY) {
+      KVECC_LAUNCH((paged_attn_golay_mfma_ragged_kernel<false>), grid, dim3(kBlock), 0, st, a);
+    } else {
+      switch (a.d) {
+        case 32: KVECC_LAUNCH((paged_attn_h84_mfma_ragged_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
+        case 64: KVECC_LAUNCH((paged_attn_h84_mfma_ragged_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
+        default: KVECC_LAUNCH((paged_attn_h84_mfma_ragged_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
+      }
+    }
+    launch_combine<__half>(a, batch * a.q_len, st);
+    return KVECC_OK;
+  }
+  const ChunkArgs &u = a;  // the uniform kernels' argument block
   if (codec == KVECC_CODEC_GOLAY_PACKED) {
-    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<true>), grid, dim3(kBlock), 0, st, a);
+    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<true>), grid, dim3(kBlock), 0, st, u);
   } else if (codec == KVECC_CODEC_GOLAY) {
-    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<false>), grid, dim3(kBlock), 0, st, a);
+    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<false>), grid, dim3(kBlock), 0, st, u);
   } else {
     switch (a.d) {
-      case 32: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
-      case 64: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
-      default: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
+      case 32: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<32>), grid, dim3(kBlock), 0, st, u); break;
+      case 64: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<64>), grid, dim3(kBlock), 0, st, u); break;
+      default: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<128>), grid, dim3(kBlock), 0, st, u); break;
     }
   }
   launch_combine<__half>(a, batch * a.q_len, st);
@@ -1085,16 +1182,20 @@ KVECC_API int64_t kvecc_paged_attention_chunk_workspace(int64_t batch, int64_t q
   return rows * cdiv(max_context_len, chunk_finest_split(rows, max_context_len)) * (head_dim + 2);
 }
 
-KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_stride,
-                                          int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
-                                          const void *k_cache, const void *v_cache,
-                                          const int32_t *block_table, const int32_t *context_lens,
-                                          const float *k_scales, const float *v_scales, void *out,
-                                          int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
-                                          int64_t head_dim, int64_t num_blocks, int64_t num_layers,
-                                          int64_t layer, int64_t block_size, int64_t max_blocks,
-                                          int64_t max_context_len, float sm_scale, int codec,
-                                          float *workspace, int64_t workspace_floats, void *stream) {
+}  // extern "C"
+
+// q_spans: null for kvecc_paged_attention_chunk, the device spans for the ragged entry (q_len its q_max).
+// Nothing but the kernels reads the spans: the launch geometry is the uniform call's.
+static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                      int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                      const void *v_cache, const int32_t *block_table,
+                                      const int32_t *context_lens, const int32_t *q_spans,
+                                      const float *k_scales, const float *v_scales, void *out, int64_t batch,
+                                      int64_t q_len, int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                      int64_t num_blocks, int64_t num_layers, int64_t layer,
+                                      int64_t block_size, int64_t max_blocks, int64_t max_context_len,
+                                      float sm_scale, int codec, float *workspace, int64_t workspace_floats,
+                                      void *stream) {
   if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
   if (batch == 0 || q_len == 0 || heads == 0) return KVECC_OK;
@@ -1104,7 +1205,9 @@ KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_str
                      (long long)q_batch_stride, (long long)q_token_stride, (long long)q_head_stride,
                      (long long)head_dim);
   // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
-  if (q_len == 1 && (heads == 1 || q_head_stride == head_dim) && (batch == 1 || q_batch_stride == heads * head_dim))
+  // (a ragged call stays here: the decode entry knows no spans)
+  if (!q_spans && q_len == 1 && (heads == 1 || q_head_stride == head_dim) &&
+      (batch == 1 || q_batch_stride == heads * head_dim))
     return kvecc_paged_attention(query, q_dtype, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, batch, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size,
                                  max_blocks, max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
@@ -1136,7 +1239,7 @@ KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_str
   if (workspace_floats < need)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: workspace %lld < %lld floats",
                      (long long)workspace_floats, (long long)need);
-  ChunkArgs a;
+  RaggedArgs a;
   a.q = query;
   a.k_cache = k_cache;
   a.v_cache = v_cache;
@@ -1164,6 +1267,7 @@ KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_str
   a.q_st = q_token_stride;
   a.q_sh = q_head_stride;
   a.cg_log2 = 0;
+  a.q_spans = q_spans;
   int64_t tiles = 1;  // matrix-core chunk kernels: 16-column tiles per (sequence, head group)
   const int64_t rows_total = num_blocks * num_layers * kv_heads * block_size;
   const int64_t cb = rows_total * (codec == KVECC_CODEC_H84            ? head_dim
@@ -1231,6 +1335,42 @@ KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_str
   }
   if (rc != KVECC_OK) return rc;
   return check_launch("paged_attention_chunk");
+}
+
+extern "C" {
+
+KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_stride,
+                                          int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                          const void *k_cache, const void *v_cache,
+                                          const int32_t *block_table, const int32_t *context_lens,
+                                          const float *k_scales, const float *v_scales, void *out,
+                                          int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
+                                          int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                          int64_t layer, int64_t block_size, int64_t max_blocks,
+                                          int64_t max_context_len, float sm_scale, int codec,
+                                          float *workspace, int64_t workspace_floats, void *stream) {
+  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, nullptr, k_scales, v_scales, out, batch, q_len, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
+}
+
+KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_batch_stride,
+                                                 int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                                 const void *k_cache, const void *v_cache,
+                                                 const int32_t *block_table, const int32_t *context_lens,
+                                                 const int32_t *q_spans, const float *k_scales,
+                                                 const float *v_scales, void *out, int64_t batch,
+                                                 int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                 int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                 int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                 int64_t max_context_len, float sm_scale, int codec,
+                                                 float *workspace, int64_t workspace_floats, void *stream) {
+  if (!q_spans) return set_error(KVECC_EINVAL, "paged_attention_chunk_ragged: null q_spans");
+  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
 }
 
 }  // extern "C"

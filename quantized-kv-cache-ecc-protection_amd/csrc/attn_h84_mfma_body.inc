@@ -1,6 +1,7 @@
 // Body of paged_attn_h84_mfma_kernel (ATTN_BODY_CHUNK 0, `a` an AttnArgs, G query
 // heads in the first G columns) and of paged_attn_h84_mfma_chunk_kernel (ATTN_BODY_CHUNK
-// 1, `a` a ChunkArgs, G = 16 (token, head) columns: ChunkMap), included by
+// 1, `a` a ChunkArgs, G = 16 (token, head) columns: ChunkMap; the ragged entry's
+// paged_attn_h84_mfma_ragged_kernel is the same text over a RaggedArgs and its ChunkMap), included by
 // attention.hip inside each kernel: the decode kernel's text is what it always
 // was, so its code is too (see ChunkArgs).
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
@@ -19,6 +20,12 @@
   const int n = lane & 15, g = lane >> 4;
 #if ATTN_BODY_CHUNK  // [column map] cm is used by every other chunk island of this file
   const ChunkMap cm(a, n);  // column n's (token, head); blockIdx.x = tile * nsplit + split
+  if constexpr (ChunkMap::kRagged) {
+    if (!cm.any) {  // every token of the tile is padding: nothing staged, no table or cache read
+      cm.put_empty(a);
+      return;
+    }
+  }
   const int64_t b = cm.b, h0 = cm.h0;
   const int64_t hk = h0 / (a.heads / a.kv_heads);
   const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns

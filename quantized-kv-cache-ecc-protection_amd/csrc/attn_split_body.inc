@@ -1,5 +1,6 @@
 // Body of paged_attn_split_kernel (ATTN_BODY_CHUNK 0, `a` an AttnArgs) and of
-// paged_attn_split_chunk_kernel (ATTN_BODY_CHUNK 1, `a` a ChunkArgs), included
+// paged_attn_split_chunk_kernel (ATTN_BODY_CHUNK 1, `a` a RaggedArgs: ChunkArgs and the
+// nullable query spans), included
 // by attention.hip inside each kernel: the decode kernel's text is what it
 // always was, so its code is too (see ChunkArgs).
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
@@ -36,6 +37,8 @@
   // b: a row of the virtual batch, token tq of sequence bt (at position context_len - q_len + tq)
   const int64_t b = a.vb0 + blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;  // query heads h0 .. h0+G-1
   const uint32_t bt = (uint32_t)b / a.q_len, tq = (uint32_t)b - bt * a.q_len;
+  const ChunkSpan sp(a, bt);  // the sequence's valid tokens (a uniform call: all q_len)
+  const bool row_ok = sp.valid(a, tq);  // a padding row reads no query and sees no key: the empty partial
 #else
   const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;  // query heads h0 .. h0+G-1
 #endif
@@ -43,7 +46,7 @@
   const int grp = threadIdx.x / W, c = threadIdx.x % W;
 #if ATTN_BODY_CHUNK  // [virtual batch] the row's key limit
   // the keys at or before the token's own position, max_context_len and the table
-  const int64_t ctx = min<int64_t>((int64_t)a.ctx_lens[bt] - (a.q_len - 1u - tq), a.ctx_cap);
+  const int64_t ctx = row_ok ? min<int64_t>(sp.lim0(a, bt) + tq, a.ctx_cap) : 0;
 #else
   const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);  // max_context_len and the table
 #endif
@@ -63,11 +66,12 @@
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int64_t di = (int64_t)c * E + e;
-      qv[j][e] = (live && di < a.d)
 #if ATTN_BODY_CHUNK  // [virtual batch] the row's query through the strides
+      qv[j][e] = (live && di < a.d && row_ok)
                      ? to_f32<T>(reinterpret_cast<const T *>(a.q)[bt * a.q_sb + tq * a.q_st + (h0 + j) * a.q_sh + di]) *
                            qscale
 #else
+      qv[j][e] = (live && di < a.d)
                      ? to_f32<T>(reinterpret_cast<const T *>(a.q)[(b * a.heads + h0 + j) * a.d + di]) * qscale
 #endif
                      : 0.0f;

@@ -637,8 +637,10 @@ struct HostShimRows {
   }
 
   // input row r of side `side` -> cache row `slot`; nib: 3 g + 3 scratch bytes
-  void store(int side, int64_t r, int64_t slot, std::vector<uint8_t> &nib) const {
-    const uint32_t key0 = (seed0 + (uint32_t)r + (uint32_t)side) * rowmul;
+  void store(int side, int64_t r, int64_t slot, std::vector<uint8_t> &nib) const { store(side, r, r, slot, nib); }
+  // the same with the injection row index `ri` apart from the input row r (ragged appends)
+  void store(int side, int64_t r, int64_t ri, int64_t slot, std::vector<uint8_t> &nib) const {
+    const uint32_t key0 = (seed0 + (uint32_t)ri + (uint32_t)side) * rowmul;
     const void *xs = x[side];
     float amax = 0.0f;
     for (int64_t j = 0; j < d; ++j) amax = std::max(amax, std::fabs(load_x(xs, x_dtype, r * d + j)));
@@ -732,6 +734,49 @@ KVECC_API int kvecc_cpu_shim_append(const void *k, const void *v, int x_dtype, i
       const int64_t blk = block_table[b * table_stride + lb];
       if (blk < 0) continue;
       rows.store(side, r, ((blk * num_layers + layer) * hkv + h) * block_size + p % block_size, nib);
+    }
+  });
+  return KVECC_OK;
+}
+
+// host twin of kvecc_shim_append_ragged: the span rule (kvecc.h "Query spans"),
+// then kvecc_cpu_shim_append's placement and skip rules on the valid tokens
+KVECC_API int kvecc_cpu_shim_append_ragged(const void *k, const void *v, int x_dtype, int64_t batch,
+                                           int64_t q_max, int64_t hkv, int64_t d, int codec,
+                                           int scale_rule, int n_bits, int inject, float ber,
+                                           int64_t seed0, void *k_cache, void *v_cache, float *k_scales,
+                                           float *v_scales, const int32_t *block_table,
+                                           int64_t table_stride, const int32_t *start_pos,
+                                           const int32_t *q_spans, int64_t num_layers,
+                                           int64_t block_size, int64_t layer, int threads) {
+  if (batch < 0 || q_max < 0 || hkv < 0 || d < 0)
+    return set_error(KVECC_EINVAL, "cpu_shim_append_ragged: negative size");
+  if (!q_spans) return set_error(KVECC_EINVAL, "cpu_shim_append_ragged: null q_spans");
+  if (batch == 0 || q_max == 0 || hkv == 0) return KVECC_OK;
+  HostShimRows rows;
+  const int rc = rows.init("cpu_shim_append_ragged", k, v, x_dtype, d, codec, scale_rule, n_bits, inject, ber, seed0,
+                           k_cache, v_cache, k_scales, v_scales, block_table, num_layers, block_size, layer);
+  if (rc != KVECC_OK) return rc;
+  if (table_stride < 1)
+    return set_error(KVECC_EINVAL, "cpu_shim_append_ragged: table stride %lld < 1", (long long)table_stride);
+  if (!start_pos) return set_error(KVECC_EINVAL, "cpu_shim_append_ragged: null pointer");
+  const int64_t per_side = batch * q_max * hkv;
+  parallel_for(2 * per_side, threads, 1, [&](int64_t b0, int64_t e0, int) {
+    std::vector<uint8_t> nib(3 * rows.g + 3);
+    for (int64_t item = b0; item < e0; ++item) {
+      const int side = (int)(item / per_side);
+      const int64_t r = item - side * per_side;  // (b * q_max + t) * hkv + h: the input row
+      const int64_t bt = r / hkv, h = r - bt * hkv;
+      const int64_t b = bt / q_max, t = bt - b * q_max;
+      const int64_t first = q_spans[3 * b], count = q_spans[3 * b + 1], base = q_spans[3 * b + 2];
+      if (first < 0 || t < first || t >= std::min(first + count, q_max)) continue;  // padding
+      const int64_t ri = (base + t - first) * hkv + h;  // dense over the valid tokens
+      if (start_pos[b] < 0) continue;
+      const int64_t p = (int64_t)start_pos[b] + (t - first), lb = p / block_size;
+      if (lb >= table_stride) continue;
+      const int64_t blk = block_table[b * table_stride + lb];
+      if (blk < 0) continue;
+      rows.store(side, r, ri, ((blk * num_layers + layer) * hkv + h) * block_size + p % block_size, nib);
     }
   });
   return KVECC_OK;
@@ -862,14 +907,15 @@ KVECC_API int kvecc_cpu_shim_read_batch(const void *k_cache, const void *v_cache
 // (reference_attention_ecc, :806-807,885-886).
 // One body for both entries: query row (b, t, h) at b*q_sb + t*q_st + h*q_sh
 // (elements), at position context_lens[b] - q_len + t, attending to the keys at
-// or before it; q_len 1 is the decode entry.
+// or before it; q_len 1 is the decode entry.  q_spans (ragged entry, kvecc.h
+// "Query spans"): row b's (first, count) replace (0, q_len).
 static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int64_t q_sh, int q_dtype,
                               const void *k_cache, const void *v_cache, const int32_t *block_table,
                               const int32_t *context_lens, const float *k_scales, const float *v_scales,
                               void *out, int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
                               int64_t head_dim, int64_t num_blocks, int64_t num_layers, int64_t layer,
                               int64_t block_size, int64_t max_blocks, int64_t max_context_len,
-                              float sm_scale, int codec, int threads) {
+                              float sm_scale, int codec, int threads, const int32_t *q_spans = nullptr) {
   if (batch < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: negative size");
   if (batch == 0 || heads == 0 || q_len == 0) return KVECC_OK;
@@ -923,11 +969,17 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
     };
     for (int64_t bh = b0; bh < e0; ++bh) {
       const int64_t b = bh / (q_len * heads), t = bh / heads % q_len, h = bh % heads, hk = h / groups;
-      for (int64_t j = 0; j < head_dim; ++j) q[j] = load_x(query, q_dtype, b * q_sb + t * q_st + h * q_sh + j);
+      // the sequence's span (null: the uniform call); a padding row reads no query and sees no key
+      const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_len;
+      const bool valid = first >= 0 && t >= first && t < std::min(first + count, q_len);
+      if (valid)
+        for (int64_t j = 0; j < head_dim; ++j) q[j] = load_x(query, q_dtype, b * q_sb + t * q_st + h * q_sh + j);
       std::fill(acc.begin(), acc.end(), 0.0f);
       float m = -INFINITY, l = 0.0f;
-      const int64_t ctx = std::min<int64_t>(std::min<int64_t>((int64_t)context_lens[b] - q_len + 1 + t, max_context_len),
-                                            max_blocks * block_size);
+      const int64_t ctx =
+          valid ? std::min<int64_t>(std::min<int64_t>((int64_t)context_lens[b] - count + 1 + (t - first), max_context_len),
+                                    max_blocks * block_size)
+                : 0;
       for (int64_t pos = 0; pos < ctx; ++pos) {
         const int32_t blk = block_table[b * max_blocks + pos / block_size];
         if (blk < 0) continue;
@@ -985,6 +1037,29 @@ KVECC_API int kvecc_cpu_paged_attention_chunk(const void *query, int64_t q_batch
                             block_table, context_lens, k_scales, v_scales, out, batch, q_len, heads, kv_heads,
                             head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
                             sm_scale, codec, threads);
+}
+
+// Ragged twin (kvecc_paged_attention_chunk_ragged): per-sequence query spans, padding rows the empty value
+KVECC_API int kvecc_cpu_paged_attention_chunk_ragged(const void *query, int64_t q_batch_stride,
+                                                     int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                                     const void *k_cache, const void *v_cache,
+                                                     const int32_t *block_table, const int32_t *context_lens,
+                                                     const int32_t *q_spans, const float *k_scales,
+                                                     const float *v_scales, void *out, int64_t batch,
+                                                     int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                     int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                     int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                     int64_t max_context_len, float sm_scale, int codec,
+                                                     int threads) {
+  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk_ragged: negative q_max");
+  if (!q_spans) return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk_ragged: null q_spans");
+  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
+      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk_ragged: bad query strides");
+  return cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                            block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads, kv_heads,
+                            head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
+                            sm_scale, codec, threads, q_spans);
 }
 
 }  // extern "C"

@@ -157,95 +157,24 @@ struct ShimAppendArgs {
 // one wave per (side, b, t, head) row; a skipped row (inactive sequence,
 // position past the table, no physical block) writes nothing but keeps its
 // running index r, so the other rows' seeds do not move
+//
+// Ragged appends (kvecc_shim_append_ragged) run a sibling kernel over the same
+// body (shim_append_body.inc): q_spans[b] = (first, count, row_base) picks the
+// valid tokens of row b (kvecc.h "Query spans").  A padding token is dead
+// before any K/V element is loaded; valid token t goes to start_pos[b] + (t -
+// first) under the running index (row_base + t - first) * hkv + h, dense over
+// the valid tokens.
 template <typename T, int CODEC, int NB>
 __global__ __launch_bounds__(kBlock) void shim_append_kernel(ShimAppendArgs a) {
-  __shared__ uint8_t nib[kWavesPerBlock][kMaxShimD + 4];
-  const ShimGeom &geo = a.geo;
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  const uint32_t per_side = a.batch * a.qlen * geo.hkv;
-  const uint32_t item = blockIdx.x * kWavesPerBlock + w;
-  const bool in_grid = item < 2 * per_side;
-  const int side = in_grid && item >= per_side ? 1 : 0;
-  const uint32_t r = in_grid ? item - side * per_side : 0;  // (b * qlen + t) * hkv + h
-  const uint32_t bt = r / geo.hkv, h = r - bt * geo.hkv;
-  const uint32_t b = bt / a.qlen, t = bt - b * a.qlen;
-  const uint32_t key0 = (a.seed0 + r + (uint32_t)side) * a.rowmul;
-  bool live = in_grid;
-  int64_t slot = 0;
-  if (live) {
-    const int32_t sp = a.start_pos[b];
-    const uint32_t p = (uint32_t)sp + t;  // sp >= 0, t < 2^31: no wrap
-    const uint32_t lb = p / geo.bs;
-    live = sp >= 0 && lb < a.tstride;
-    if (live) {
-      const int64_t blk = geo.table[(int64_t)b * a.tstride + lb];
-      live = blk >= 0;
-      slot = ((blk * geo.layers + geo.layer) * geo.hkv + h) * geo.bs + (p - lb * geo.bs);
-    }
-  }
-
-  constexpr int kPer = kMaxShimD / kWave;
-  float v[kPer];
-  float amax = 0.0f;
-  if (live) {
-    const T *x = reinterpret_cast<const T *>(a.x[side]) + (int64_t)b * a.xb[side] + (int64_t)t * a.xs[side] +
-                 (int64_t)h * a.xh[side];
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const uint32_t e = lane + i * kWave;
-      v[i] = e < geo.d ? to_f32<T>(x[e]) : 0.0f;
-      amax = fmaxf(amax, fabsf(v[i]));
-    }
-  }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, kWave));
-  const float scale = row_scale(amax, a.scale_rule);
-  if (live && lane == 0) a.scales[side][slot] = scale;
-  const bool recip = sizeof(T) == 2 && recip_ok(scale);
-  const float inv = div_rn(1.0f, scale);
-  auto quant = [&](float x) {
-    return recip ? nibble_of_quotient(div_recip(x, scale, inv)) : quantize_nibble(x, scale);
-  };
-
-  constexpr bool kGolay = CODEC == KVECC_CODEC_GOLAY || CODEC == KVECC_CODEC_GOLAY_PACKED;
-  if (!kGolay) {
-    if (!live) return;
-    uint8_t *c = reinterpret_cast<uint8_t *>(a.cache[side]) + slot * geo.g;
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const uint32_t e = lane + i * kWave;
-      if (e < geo.d) {
-        uint32_t cw = encode_nibble(quant(v[i]), CODEC);
-        if (a.inject) cw ^= philox_flip_mask<NB>(key0 + e * a.nbits, e, a.thr, a.nb_eff);
-        c[e] = (uint8_t)cw;
-      }
-    }
-    return;
-  }
-  // Golay: nibbles through LDS, one lane per codeword of 3; skipped rows reach the barrier too
-  if (live) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const uint32_t e = lane + i * kWave;
-      if (e < geo.d) nib[w][e] = (uint8_t)quant(v[i]);
-    }
-    if ((uint32_t)lane < 3 * geo.g - geo.d) nib[w][geo.d + lane] = 0;  // per-head zero padding
-  }
-  __syncthreads();
-  if (!live) return;
-  for (uint32_t k = lane; k < geo.g; k += kWave) {
-    const uint32_t dw = golay_pack(nib[w][3 * k], nib[w][3 * k + 1], nib[w][3 * k + 2]);
-    uint32_t cw = dw | golay_parity12(dw) << 12;
-    if (a.inject) cw ^= philox_flip_mask<NB>(key0 + k * a.nbits, k, a.thr, a.nb_eff);
-    if (CODEC == KVECC_CODEC_GOLAY_PACKED) {
-      uint8_t *c = reinterpret_cast<uint8_t *>(a.cache[side]) + slot * KVECC_GOLAY_PACKED_ROW(geo.g) + 3 * k;
-      c[0] = (uint8_t)cw;
-      c[1] = (uint8_t)(cw >> 8);
-      c[2] = (uint8_t)(cw >> 16);
-    } else {
-      reinterpret_cast<int32_t *>(a.cache[side])[slot * geo.g + k] = (int32_t)cw;
-    }
-  }
+#define SHIM_APPEND_RAGGED 0
+#include "shim_append_body.inc"
+#undef SHIM_APPEND_RAGGED
+}
+template <typename T, int CODEC, int NB>
+__global__ __launch_bounds__(kBlock) void shim_append_ragged_kernel(ShimAppendArgs a, const int32_t *q_spans) {
+#define SHIM_APPEND_RAGGED 1
+#include "shim_append_body.inc"
+#undef SHIM_APPEND_RAGGED
 }
 
 struct ShimReadArgs {
@@ -978,25 +907,30 @@ static void launch_write(int codec, const ShimWriteArgs &a, unsigned grid, hipSt
 }
 
 template <typename T, int CODEC>
-static void launch_append_nb(const ShimAppendArgs &a, unsigned grid, hipStream_t st) {
+static void launch_append_nb(const ShimAppendArgs &a, const int32_t *q_spans, unsigned grid, hipStream_t st) {
   constexpr int NB = CODEC == KVECC_CODEC_GOLAY || CODEC == KVECC_CODEC_GOLAY_PACKED ? 24
                      : CODEC == KVECC_CODEC_H84 ? 8
                      : CODEC == KVECC_CODEC_H74 ? 7
                                                 : 4;
-  if (a.nb_eff == NB)
+  if (q_spans) {
+    if (a.nb_eff == NB)
+      KVECC_LAUNCH((shim_append_ragged_kernel<T, CODEC, NB>), dim3(grid), dim3(kBlock), 0, st, a, q_spans);
+    else
+      KVECC_LAUNCH((shim_append_ragged_kernel<T, CODEC, -1>), dim3(grid), dim3(kBlock), 0, st, a, q_spans);
+  } else if (a.nb_eff == NB)
     KVECC_LAUNCH((shim_append_kernel<T, CODEC, NB>), dim3(grid), dim3(kBlock), 0, st, a);
   else
     KVECC_LAUNCH((shim_append_kernel<T, CODEC, -1>), dim3(grid), dim3(kBlock), 0, st, a);
 }
 
 template <typename T>
-static void launch_append(int codec, const ShimAppendArgs &a, unsigned grid, hipStream_t st) {
+static void launch_append(int codec, const ShimAppendArgs &a, const int32_t *q_spans, unsigned grid, hipStream_t st) {
   switch (codec) {
-    case KVECC_CODEC_NONE: launch_append_nb<T, KVECC_CODEC_NONE>(a, grid, st); break;
-    case KVECC_CODEC_H74: launch_append_nb<T, KVECC_CODEC_H74>(a, grid, st); break;
-    case KVECC_CODEC_H84: launch_append_nb<T, KVECC_CODEC_H84>(a, grid, st); break;
-    case KVECC_CODEC_GOLAY_PACKED: launch_append_nb<T, KVECC_CODEC_GOLAY_PACKED>(a, grid, st); break;
-    default: launch_append_nb<T, KVECC_CODEC_GOLAY>(a, grid, st); break;
+    case KVECC_CODEC_NONE: launch_append_nb<T, KVECC_CODEC_NONE>(a, q_spans, grid, st); break;
+    case KVECC_CODEC_H74: launch_append_nb<T, KVECC_CODEC_H74>(a, q_spans, grid, st); break;
+    case KVECC_CODEC_H84: launch_append_nb<T, KVECC_CODEC_H84>(a, q_spans, grid, st); break;
+    case KVECC_CODEC_GOLAY_PACKED: launch_append_nb<T, KVECC_CODEC_GOLAY_PACKED>(a, q_spans, grid, st); break;
+    default: launch_append_nb<T, KVECC_CODEC_GOLAY>(a, q_spans, grid, st); break;
   }
 }
 
@@ -1191,15 +1125,15 @@ KVECC_API int kvecc_shim_write_strided(const void *k, const void *v, int64_t k_b
                          num_layers, block_size, layer, stream);
 }
 
-KVECC_API int kvecc_shim_append(const void *k, const void *v, int64_t k_batch_stride,
-                                int64_t k_seq_stride, int64_t k_head_stride, int64_t v_batch_stride,
-                                int64_t v_seq_stride, int64_t v_head_stride, int x_dtype, int64_t batch,
-                                int64_t q_len, int64_t hkv, int64_t d, int codec, int scale_rule,
-                                int n_bits, int inject, float ber, int64_t seed0, void *k_cache,
-                                void *v_cache, float *k_scales, float *v_scales,
-                                const int32_t *block_table, int64_t table_stride,
-                                const int32_t *start_pos, int64_t num_layers, int64_t block_size,
-                                int64_t layer, void *stream) {
+// q_spans: null for kvecc_shim_append, the device spans for kvecc_shim_append_ragged (q_len its q_max)
+static int shim_append_impl(const void *k, const void *v, int64_t k_batch_stride, int64_t k_seq_stride,
+                            int64_t k_head_stride, int64_t v_batch_stride, int64_t v_seq_stride,
+                            int64_t v_head_stride, int x_dtype, int64_t batch, int64_t q_len, int64_t hkv,
+                            int64_t d, int codec, int scale_rule, int n_bits, int inject, float ber,
+                            int64_t seed0, void *k_cache, void *v_cache, float *k_scales, float *v_scales,
+                            const int32_t *block_table, int64_t table_stride, const int32_t *start_pos,
+                            const int32_t *q_spans, int64_t num_layers, int64_t block_size, int64_t layer,
+                            void *stream) {
   if (batch < 0 || q_len < 0 || hkv < 0 || d < 0) return set_error(KVECC_EINVAL, "shim_append: negative size");
   if (batch == 0 || q_len == 0 || hkv == 0) return KVECC_OK;
   if (d < 1 || d > kMaxShimD)
@@ -1257,11 +1191,42 @@ KVECC_API int kvecc_shim_append(const void *k, const void *v, int64_t k_batch_st
   const unsigned blocks = (unsigned)cdiv(2 * batch * q_len * hkv, kWavesPerBlock);
   hipStream_t st = as_stream(stream);
   switch (x_dtype) {
-    case KVECC_F32: launch_append<float>(codec, a, blocks, st); break;
-    case KVECC_F16: launch_append<__half>(codec, a, blocks, st); break;
-    default: launch_append<__hip_bfloat16>(codec, a, blocks, st); break;
+    case KVECC_F32: launch_append<float>(codec, a, q_spans, blocks, st); break;
+    case KVECC_F16: launch_append<__half>(codec, a, q_spans, blocks, st); break;
+    default: launch_append<__hip_bfloat16>(codec, a, q_spans, blocks, st); break;
   }
   return check_launch("shim_append");
+}
+
+KVECC_API int kvecc_shim_append(const void *k, const void *v, int64_t k_batch_stride,
+                                int64_t k_seq_stride, int64_t k_head_stride, int64_t v_batch_stride,
+                                int64_t v_seq_stride, int64_t v_head_stride, int x_dtype, int64_t batch,
+                                int64_t q_len, int64_t hkv, int64_t d, int codec, int scale_rule,
+                                int n_bits, int inject, float ber, int64_t seed0, void *k_cache,
+                                void *v_cache, float *k_scales, float *v_scales,
+                                const int32_t *block_table, int64_t table_stride,
+                                const int32_t *start_pos, int64_t num_layers, int64_t block_size,
+                                int64_t layer, void *stream) {
+  return shim_append_impl(k, v, k_batch_stride, k_seq_stride, k_head_stride, v_batch_stride, v_seq_stride,
+                          v_head_stride, x_dtype, batch, q_len, hkv, d, codec, scale_rule, n_bits, inject, ber,
+                          seed0, k_cache, v_cache, k_scales, v_scales, block_table, table_stride, start_pos,
+                          nullptr, num_layers, block_size, layer, stream);
+}
+
+KVECC_API int kvecc_shim_append_ragged(const void *k, const void *v, int64_t k_batch_stride,
+                                       int64_t k_seq_stride, int64_t k_head_stride, int64_t v_batch_stride,
+                                       int64_t v_seq_stride, int64_t v_head_stride, int x_dtype,
+                                       int64_t batch, int64_t q_max, int64_t hkv, int64_t d, int codec,
+                                       int scale_rule, int n_bits, int inject, float ber, int64_t seed0,
+                                       void *k_cache, void *v_cache, float *k_scales, float *v_scales,
+                                       const int32_t *block_table, int64_t table_stride,
+                                       const int32_t *start_pos, const int32_t *q_spans,
+                                       int64_t num_layers, int64_t block_size, int64_t layer, void *stream) {
+  if (!q_spans) return set_error(KVECC_EINVAL, "shim_append_ragged: null q_spans");
+  return shim_append_impl(k, v, k_batch_stride, k_seq_stride, k_head_stride, v_batch_stride, v_seq_stride,
+                          v_head_stride, x_dtype, batch, q_max, hkv, d, codec, scale_rule, n_bits, inject, ber,
+                          seed0, k_cache, v_cache, k_scales, v_scales, block_table, table_stride, start_pos,
+                          q_spans, num_layers, block_size, layer, stream);
 }
 
 static int shim_read_impl(const void *k_cache, const void *v_cache, const float *k_scales,

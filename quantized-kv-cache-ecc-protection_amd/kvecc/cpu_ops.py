@@ -519,6 +519,26 @@ def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table,
               int(block_size), int(layer), NUM_THREADS)
 
 
+def shim_append_ragged_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
+                               block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, q_spans,
+                               scale_rule=None):
+    """Host twin of ops.shim_append_ragged_tensors (kvecc_cpu_shim_append_ragged):
+    same arguments and rules; q_spans is a host tensor, K/V are made contiguous."""
+    from .ops import _check_q_spans, _check_shim_append_args, _head_rows
+    if k.device.type != "cpu":
+        raise ValueError(f"the cpu backend writes host tensors, k is on {k.device}")
+    batch, q_max = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
+                                           num_layers, block_size, hkv, d, layer, codec)
+    _check_q_spans(q_spans, batch, k.device)
+    k4 = _head_rows(k, batch, q_max, hkv, d).contiguous()
+    v4 = _head_rows(v, batch, q_max, hkv, d).contiguous()
+    _lib.call("kvecc_cpu_shim_append_ragged", _ptr(k4), _ptr(v4), _DT[k.dtype], batch, q_max, int(hkv), int(d),
+              SHIM_CODECS[codec], _lib.scale_rule_code(scale_rule, DEFAULT_SCALE_RULE), int(n_bits),
+              int(bool(inject)), float(ber), int(seed0), _ptr(k_cache), _ptr(v_cache), _ptr(k_scales),
+              _ptr(v_scales), _ptr(block_table), block_table.shape[1], _ptr(start_pos), _ptr(q_spans),
+              int(num_layers), int(block_size), int(layer), NUM_THREADS)
+
+
 def shim_read(manager, layer, ctx, codec, interp, out_dtype, stats=None, seq_id=0):
     return shim_read_tensors(manager.k_cache, manager.v_cache, manager.k_scales, manager.v_scales,
                              manager.block_table[seq_id], ctx, manager.num_kv_heads, manager.head_dim,
@@ -577,15 +597,23 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
 
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
+                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None):
     """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
-    from .ops import _check_attention_chunk_args
+    from .ops import _check_attention_chunk_args, _check_q_spans
     _check_cpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
     batch, q_len, heads, head_dim = query.shape
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
+        _lib.call("kvecc_cpu_paged_attention_chunk_ragged", _ptr(query), query.stride(0), query.stride(1),
+                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+                  int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
+        return out
     _lib.call("kvecc_cpu_paged_attention_chunk", _ptr(query), query.stride(0), query.stride(1),
               query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
               _ptr(context_lens), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads,
@@ -629,7 +657,8 @@ def paged_attention_ecc(query, k_cache, v_cache, block_table, context_lens, k_sc
 # Packed Golay storage (host twins of ops.golay_encode_packed / decode_packed)
 # ============================================================================
 
-from .ops import pack_nibbles, tiled_empty_to_zero, unpack_nibbles  # noqa: E402  (pure torch)
+from .ops import (pack_nibbles, query_spans, query_spans_from_mask, tiled_empty_to_zero,  # noqa: E402,F401
+                  unpack_nibbles)  # (pure torch)
 
 
 def golay_encode_packed(nibbles: torch.Tensor, m: int) -> torch.Tensor:

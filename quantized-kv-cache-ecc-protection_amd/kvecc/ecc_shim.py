@@ -232,6 +232,15 @@ class SimpleBlockManager:
         for b in range(batch):
             row[b] += num_tokens
 
+    def advance_spans(self, layer, batch, spans, counts):
+        """The per-sequence form of advance: sequence b grew by its span's count.
+        The device side adds the count column of `spans` (the device [.., 3] span
+        buffer, no host read), the host mirror the host `counts`."""
+        self.ctx_lens[layer, :batch] += spans[:batch, 1]
+        row = self._host_lens[layer]
+        for b in range(batch):
+            row[b] += counts[b]
+
     def extend(self, seq_id, new_len):
         """Blocks to cover new_len tokens of seq_id; the ones it has stay as they are."""
         if new_len > self.seq_to_len.get(seq_id, 0):
@@ -349,6 +358,10 @@ class ECCBackend:
         self._injection_count = 0
         self._total_values = 0
         self._stats = self.codec_backend.new_stats(manager.k_cache.device)  # backend counters
+        # ragged batches (set_query_spans): host (counts, firsts) and the
+        # persistent device buffer [max_seqs, 3] the kernels read
+        self._spans = None
+        self._span_buf = None
 
     # counters read lazily (one sync) -------------------------------------------
     @property
@@ -438,16 +451,71 @@ class ECCBackend:
         if batch > self.manager.max_seqs:
             raise ValueError(f"append mode holds {self.manager.max_seqs} sequences, got a batch of {batch}")
 
+    def set_query_spans(self, counts, firsts=None):
+        """Hold per-sequence query spans for every following append-mode forward
+        (None clears them): sequence b's valid tokens are [firsts[b], firsts[b] +
+        counts[b]) of its row.  The spans go to the device once, here; a forward
+        reads the buffer and copies nothing from the host."""
+        if counts is None:
+            self._spans = None
+            return
+        if not self.append:
+            raise ValueError("query spans need cache_mode='append'")
+        if not hasattr(self.codec_backend, "shim_append_ragged_tensors"):
+            raise ValueError("this backend has no ragged append (shim_append_ragged_tensors)")
+        counts = [int(c) for c in counts]
+        firsts = [0] * len(counts) if firsts is None else [int(f) for f in firsts]
+        self.check_append_batch(len(counts))
+        spans = self.codec_backend.query_spans(counts, firsts)  # ValueError: a negative entry, lengths
+        if self._span_buf is None:
+            self._span_buf = torch.zeros((self.manager.max_seqs, 3), dtype=torch.int32,
+                                         device=self.manager.k_cache.device)
+        self._span_buf[:len(counts)].copy_(spans)
+        self._spans = (counts, firsts)
+
+    def _check_spans(self, batch, q_max):
+        counts, firsts = self._spans
+        if len(counts) != batch:
+            raise ValueError(f"query spans hold {len(counts)} sequences, the forward has a batch of {batch}")
+        for b, (f, c) in enumerate(zip(firsts, counts)):
+            if f + c > q_max:
+                raise ValueError(f"query span {b}: first {f} + count {c} > the forward's {q_max} tokens")
+
     def _append_write(self, k, v, layer_idx):
         """Batch row b is sequence b: its q_len tokens go behind the layer's
         current length of that sequence, every sequence in one launch.  The
-        start positions are the manager's device lengths; nothing is read back."""
+        start positions are the manager's device lengths; nothing is read back.
+        With query spans held, only each row's valid tokens are appended."""
         cfg, mgr = self.config, self.manager
         batch, q_len = k.shape[0], k.shape[1]
         self.check_append_batch(batch)
         if k.dtype != v.dtype or k.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise TypeError(f"append mode: K/V dtype {k.dtype}/{v.dtype} has no fused write")
         d, hk = self.head_dim, self.num_kv_heads
+        if self._spans is not None:
+            self._check_spans(batch, q_len)  # before anything is written
+            counts = self._spans[0]
+            total = sum(counts)
+            self._total_values += 2 * total * hk * d
+            for b, n in enumerate(mgr.layer_lens(layer_idx, batch)):
+                mgr.extend(b, n + counts[b])  # count 0: nothing allocated
+            inject = cfg.inject_errors and cfg.ber > 0
+            seed0 = cfg.seed + self._injection_count
+            spans = self._span_buf[:batch]
+            if self._traced():
+                torch.ops.kvecc.shim_append_ragged(
+                    k, v, mgr.k_cache, mgr.v_cache, mgr.k_scales, mgr.v_scales, mgr.block_table[:batch],
+                    mgr.ctx_lens[layer_idx, :batch], spans, mgr.num_layers, mgr.block_size, hk, d, layer_idx,
+                    mgr.shim_codec, _N_BITS[cfg.codec], inject, cfg.ber, seed0, cfg.scale_rule)
+            else:
+                self.codec_backend.shim_append_ragged_tensors(
+                    k, v, mgr.k_cache, mgr.v_cache, mgr.k_scales, mgr.v_scales, mgr.block_table[:batch],
+                    mgr.ctx_lens[layer_idx, :batch], mgr.num_layers, mgr.block_size, hk, d, layer_idx,
+                    mgr.shim_codec, _N_BITS[cfg.codec], inject, cfg.ber, seed0, spans, cfg.scale_rule)
+            mgr.advance_spans(layer_idx, batch, self._span_buf, counts)
+            if inject:
+                self._injection_count += total * hk  # dense seeds: rows written
+            return
         self._total_values += 2 * batch * q_len * hk * d
         for b, n in enumerate(mgr.layer_lens(layer_idx, batch)):
             mgr.extend(b, n + q_len)
@@ -488,11 +556,26 @@ class ECCBackend:
                 q1, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx)
             return out.unsqueeze(2)
+        spans = None
+        if self._spans is not None:
+            self._check_spans(b, q_len)
+            spans = self._span_buf[:b]
         if q_len > 1 and cfg.chunk_attention and cfg.codec in ("hamming84", "golay") and not interp \
                 and not cfg.decode_stats and d <= 256:
             # prefill / chunk / verify step on the chunked causal kernel: q read
             # in place as [batch, q_len, heads, d], no dense K / V, no statistics
             qt = q.transpose(1, 2)
+            if spans is not None:  # ragged: padding rows come out as the kernel's empty value
+                if self._traced():
+                    out = torch.ops.kvecc.paged_attention_chunk_ragged(
+                        qt, mgr.k_cache, mgr.v_cache, table, dev_lens, spans, mgr.k_scales, mgr.v_scales,
+                        layer_idx, mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, ctx)
+                    return out.transpose(1, 2)
+                out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+                self.codec_backend.paged_attention_chunk_into(
+                    qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                    mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx, q_spans=spans)
+                return out.transpose(1, 2)
             if self._traced():
                 out = torch.ops.kvecc.paged_attention_chunk(qt, mgr.k_cache, mgr.v_cache, table, dev_lens,
                                                             mgr.k_scales, mgr.v_scales, layer_idx,
@@ -517,8 +600,18 @@ class ECCBackend:
             k_t = k_t.repeat_interleave(self.num_kv_groups, dim=1)
             v_t = v_t.repeat_interleave(self.num_kv_groups, dim=1)
         # query t of sequence b sits at position start_b + t and sees keys j <= start_b + t
-        qpos = (dev_lens - q_len).view(b, 1, 1) + torch.arange(q_len, device=q.device).view(1, q_len, 1)
-        mask = torch.arange(ctx, device=q.device).view(1, 1, ctx) <= qpos
+        tq = torch.arange(q_len, device=q.device).view(1, q_len, 1)
+        keys = torch.arange(ctx, device=q.device).view(1, 1, ctx)
+        if spans is not None:
+            # valid token t of sequence b sits at ctx_b - count_b + (t - first_b); a
+            # padding row sees key 0 alone, so that it comes out finite
+            first, count = spans[:, 0].view(b, 1, 1), spans[:, 1].view(b, 1, 1)
+            valid = (tq >= first) & (tq < first + count)
+            qpos = (dev_lens.view(b, 1, 1) - count) + (tq - first)
+            mask = torch.where(valid, keys <= qpos, keys == 0)
+            return F.scaled_dot_product_attention(q, k_t, v_t, attn_mask=mask.unsqueeze(1))
+        qpos = (dev_lens - q_len).view(b, 1, 1) + tq
+        mask = keys <= qpos
         return F.scaled_dot_product_attention(q, k_t, v_t, attn_mask=mask.unsqueeze(1))
 
     def _traced(self):
@@ -736,6 +829,10 @@ class ECCPagedAttentionShim(nn.Module):
             self.backend.check_append_batch(b)
             start = self.backend.manager.ctx_lens[self.layer_idx, :b].to(torch.long)
             position_ids = start.unsqueeze(1) + torch.arange(s, device=hidden_states.device)
+            if self.backend._spans is not None:  # ragged: token t of row b sits at start_b + max(t - first_b, 0)
+                self.backend._check_spans(b, s)
+                first = self.backend._span_buf[:b, 0].to(torch.long)
+                position_ids = (position_ids - first.unsqueeze(1)).maximum(start.unsqueeze(1))
         elif position_ids is None:
             position_ids = torch.arange(s, device=hidden_states.device).unsqueeze(0).expand(b, -1)
         cos, sin = self.rotary_emb(v, position_ids)
@@ -895,11 +992,28 @@ def patch_model_with_ecc_attention(model, config, num_blocks=256):
 
 
 def reset_ecc_cache(model):
-    """Fresh cache and counters for a new text (ecc_shim.py:1614-1624)."""
+    """Fresh cache and counters for a new text (ecc_shim.py:1614-1624); query
+    spans held for ragged batches are cleared."""
     if hasattr(model, "_ecc_block_manager"):
         model._ecc_block_manager.reset()
     if hasattr(model, "_ecc_backend"):
         model._ecc_backend.reset_stats()
+        model._ecc_backend.set_query_spans(None)
+
+
+def set_ecc_query_spans(model, counts, firsts=None):
+    """Ragged batches in append mode (no reference counterpart): tell the patched
+    model which tokens of every following forward's [batch, q_max] rows are real.
+    counts / firsts are host integer sequences of length batch -- row b's valid
+    tokens are [firsts[b], firsts[b] + counts[b]), firsts defaulting to 0 (right
+    padding); kvecc.query_spans_from_mask reads them off an attention mask.
+    Padding tokens are not cached and nothing attends to them; a count of 0 holds
+    a finished sequence still.  The spans are uploaded once, here, and hold until
+    replaced, cleared (counts=None) or reset_ecc_cache.  Pass matching
+    position_ids to the model (LLaMA shims derive them when given none)."""
+    if not hasattr(model, "_ecc_backend"):
+        raise ValueError("model is not patched with patch_model_with_ecc_attention")
+    model._ecc_backend.set_query_spans(counts, firsts)
 
 
 def get_ecc_stats(model):

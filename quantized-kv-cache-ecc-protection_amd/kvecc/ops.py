@@ -848,6 +848,81 @@ def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table,
               int(block_size), int(layer), _stream(k.device))
 
 
+def _check_q_spans(q_spans, batch, device):
+    """q_spans of a ragged call (both backends): int32 [batch, 3] (first, count,
+    row_base), contiguous, on the K / query tensor's device."""
+    if not isinstance(q_spans, torch.Tensor) or q_spans.dtype != torch.int32 or \
+            tuple(q_spans.shape) != (batch, 3):
+        got = f"{q_spans.dtype} {tuple(q_spans.shape)}" if isinstance(q_spans, torch.Tensor) else type(q_spans)
+        raise ValueError(f"q_spans must be an int32 [{batch}, 3] tensor, got {got}")
+    if q_spans.device != device:
+        raise ValueError(f"q_spans is on {q_spans.device}, expected {device}")
+    if not q_spans.is_contiguous():
+        raise ValueError("q_spans must be contiguous")
+
+
+def query_spans(counts, firsts=None, q_max=None, device=None):
+    """The [batch, 3] int32 span tensor of a ragged call from host integers:
+    row b is (firsts[b], counts[b], row_base[b]) with row_base the exclusive
+    prefix sum of the counts.  firsts defaults to 0 (right padding).  A negative
+    entry, or first + count > q_max when q_max is given, raises ValueError."""
+    counts = [int(c) for c in counts]
+    firsts = [0] * len(counts) if firsts is None else [int(f) for f in firsts]
+    if len(firsts) != len(counts):
+        raise ValueError(f"{len(counts)} counts but {len(firsts)} firsts")
+    rows, base = [], 0
+    for b, (f, c) in enumerate(zip(firsts, counts)):
+        if f < 0 or c < 0:
+            raise ValueError(f"span {b}: negative first {f} or count {c}")
+        if q_max is not None and f + c > int(q_max):
+            raise ValueError(f"span {b}: first {f} + count {c} > q_max {q_max}")
+        rows.append((f, c, base))
+        base += c
+    t = torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 3)
+    return t if device is None else t.to(device)
+
+
+def query_spans_from_mask(mask):
+    """(counts, firsts) as host integer lists from a 2-D [batch, q_max] 0/1
+    mask (an HF attention_mask of the forward's tokens), read with one host
+    copy.  A row's ones must be one contiguous run (ValueError otherwise); an
+    all-zero row is count 0."""
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 2:
+        raise ValueError("mask must be a 2-D [batch, q_max] tensor")
+    rows = (mask != 0).to("cpu").tolist()
+    counts, firsts = [], []
+    for b, row in enumerate(rows):
+        n = sum(row)
+        f = row.index(True) if n else 0
+        if any(not x for x in row[f:f + n]):
+            raise ValueError(f"mask row {b} is not one contiguous run of ones")
+        counts.append(n)
+        firsts.append(f)
+    return counts, firsts
+
+
+def shim_append_ragged_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
+                               block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, q_spans,
+                               scale_rule=None):
+    """shim_append_tensors over query spans (kvecc_shim_append_ragged): K, V
+    [batch, q_max, ...] and q_spans int32 [batch, 3] on the device.  Valid token
+    t of sequence b lands at start_pos[b] + (t - first); padding tokens write
+    nothing and are never loaded; seeds are dense over the valid tokens."""
+    if not k.is_cuda:
+        raise ValueError(f"the hip backend writes GPU tensors, k is on {k.device}")
+    batch, q_max = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
+                                           num_layers, block_size, hkv, d, layer, codec)
+    _check_q_spans(q_spans, batch, k.device)
+    k4 = _head_rows(k, batch, q_max, hkv, d)
+    v4 = _head_rows(v, batch, q_max, hkv, d)
+    _lib.call("kvecc_shim_append_ragged", _ptr(k4), _ptr(v4), k4.stride(0), k4.stride(1), k4.stride(2),
+              v4.stride(0), v4.stride(1), v4.stride(2), _DT[k.dtype], batch, q_max, int(hkv), int(d),
+              SHIM_CODECS[codec], _lib.scale_rule_code(scale_rule, DEFAULT_SCALE_RULE), int(n_bits),
+              int(bool(inject)), float(ber), int(seed0), _ptr(k_cache), _ptr(v_cache), _ptr(k_scales),
+              _ptr(v_scales), _ptr(block_table), block_table.shape[1], _ptr(start_pos), _ptr(q_spans),
+              int(num_layers), int(block_size), int(layer), _stream(k.device))
+
+
 def shim_read_batch(k_cache, v_cache, k_scales, v_scales, block_table, ctx, head_dim, layer, codec,
                     out_dtype, stats=None, interp=False, out=None):
     """The shim's fused read (gather -> decode -> dequantize, ecc_shim.py:990-1071)
@@ -1015,7 +1090,7 @@ def _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_le
 
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
+                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None):
     """kvecc_paged_attention_chunk: q_len query tokens per sequence, causal (include/kvecc.h).
 
     query [B, q_len, H, D] with any strides and a unit innermost one (the
@@ -1023,16 +1098,30 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     are read in place); out contiguous [B, q_len, H, D] in the query's dtype.
     context_lens counts the chunk's own tokens: query t sits at position
     context_lens[b] - q_len + t.  Arguments are validated as in
-    paged_attention_into and the same cached workspace is used."""
+    paged_attention_into and the same cached workspace is used.
+
+    q_spans (int32 [B, 3] on the device, see query_spans) makes the call ragged
+    (kvecc_paged_attention_chunk_ragged): q_len is the rectangle's q_max,
+    context_lens counts each sequence's own valid tokens, padding rows come out
+    as the empty value and their query elements are never read."""
     _check_gpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
     batch, q_len, heads, head_dim = query.shape
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
     mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
     ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
     ws = _attn_workspace(query.device, ws_n)
+    if q_spans is not None:
+        _lib.call("kvecc_paged_attention_chunk_ragged", _ptr(query), query.stride(0), query.stride(1),
+                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+                  mcl, float(sm_scale), SHIM_CODECS[codec], _ptr(ws), ws.numel(), _stream(query.device))
+        return out
     _lib.call("kvecc_paged_attention_chunk", _ptr(query), query.stride(0), query.stride(1), query.stride(2),
               _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table), _ptr(context_lens),
               _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads, head_dim, num_blocks,
@@ -1042,9 +1131,10 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
 
 
 def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                          layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0):
+                          layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0,
+                          q_spans=None):
     """paged_attention_chunk_into with a fresh [B, q_len, H, D] output; on the
-    GPU or, for host tensors, through the host twin."""
+    GPU or, for host tensors, through the host twin.  q_spans: a ragged call."""
     if sm_scale is None:
         sm_scale = 1.0 / math.sqrt(query.shape[-1])
     out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
@@ -1052,10 +1142,10 @@ def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_
         from . import cpu_ops
         return cpu_ops.paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
                                                   v_scales, out, layer_idx, block_size, sm_scale, codec,
-                                                  max_context_len=max_context_len)
+                                                  max_context_len=max_context_len, q_spans=q_spans)
     return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                       out, layer_idx, block_size, sm_scale, codec,
-                                      max_context_len=max_context_len)
+                                      max_context_len=max_context_len, q_spans=q_spans)
 
 
 def _conform(t, dtype):

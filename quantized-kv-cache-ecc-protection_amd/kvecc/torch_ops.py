@@ -305,6 +305,25 @@ def _(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_la
     return None
 
 
+@torch.library.custom_op("kvecc::shim_append_ragged", mutates_args=("k_cache", "v_cache", "k_scales", "v_scales"),
+                         device_types=_DEV)
+def shim_append_ragged(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, k_scales: Tensor,
+                       v_scales: Tensor, block_table: Tensor, start_pos: Tensor, q_spans: Tensor,
+                       num_layers: int, block_size: int, hkv: int, d: int, layer: int, codec: str, n_bits: int,
+                       inject: bool, ber: float, seed0: int, scale_rule: Optional[str] = None) -> None:
+    """shim_append over per-sequence query spans: valid token t of sequence b at
+    start_pos[b] + (t - first) (kvecc_shim_append_ragged; no reference counterpart)."""
+    _be(k).shim_append_ragged_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
+                                      num_layers, block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0,
+                                      q_spans, scale_rule)
+
+
+@shim_append_ragged.register_fake
+def _(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, q_spans, num_layers, block_size, hkv, d,
+      layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
+    return None
+
+
 @torch.library.custom_op("kvecc::shim_read", mutates_args=("stats",), device_types=_DEV)
 def shim_read(k_cache: Tensor, v_cache: Tensor, k_scales: Tensor, v_scales: Tensor, table: Tensor, ctx: int,
               hkv: int, d: int, num_layers: int, block_size: int, layer: int, codec: str, interp: bool,
@@ -359,9 +378,30 @@ def _(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, la
     return query.new_empty(query.shape)
 
 
+@torch.library.custom_op("kvecc::paged_attention_chunk_ragged", mutates_args=(), device_types=_DEV)
+def paged_attention_chunk_ragged(query: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor,
+                                 context_lens: Tensor, q_spans: Tensor, k_scales: Tensor, v_scales: Tensor,
+                                 layer_idx: int, block_size: int, sm_scale: float, codec: str,
+                                 max_context_len: int = 0) -> Tensor:
+    """paged_attention_chunk over per-sequence query spans: query [B, q_max, H, D],
+    padding rows the empty value (kvecc_paged_attention_chunk_ragged)."""
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    _be(query).paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
+                                          v_scales, out, layer_idx, block_size, sm_scale, codec,
+                                          max_context_len=max_context_len, q_spans=q_spans)
+    return out
+
+
+@paged_attention_chunk_ragged.register_fake
+def _(query, k_cache, v_cache, block_table, context_lens, q_spans, k_scales, v_scales, layer_idx, block_size,
+      sm_scale, codec, max_context_len=0):
+    return query.new_empty(query.shape)
+
+
 OPS: List[str] = ["hamming74_encode", "hamming84_encode", "hamming74_decode", "hamming84_decode",
                   "golay_encode", "golay_decode", "golay_encode_rows", "golay_decode_rows",
                   "inject_bit_errors", "inject_bit_errors_", "interpolate_double_errors",
                   "fused_quantize_encode", "fused_decode_dequantize_hamming84", "shim_write", "shim_append",
-                  "shim_read", "paged_attention", "paged_attention_chunk"]
+                  "shim_append_ragged", "shim_read", "paged_attention", "paged_attention_chunk",
+                  "paged_attention_chunk_ragged"]
 _ = _lib  # the operators bind libkvecc.so lazily, on first call

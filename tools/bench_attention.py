@@ -10,7 +10,17 @@ the context) three ways at the same shape and data, and prints all three: the
 chunked causal kernel (paged_attention_chunk_into), N decode calls (one per
 chunk token, at its own context length), and the path the shim takes without
 chunk_attention, composed as ECCBackend._append_attend composes it:
-shim_read_batch + repeat_interleave + the causal mask + SDPA.
+shim_read_batch + repeat_interleave + the causal mask + SDPA.  --only chunk
+times the first alone.
+
+--q-spans c0,c1,... (with --q-len as q_max; one count per sequence, right-aligned:
+first = q_max - count) times the ragged call (q_spans) against the uniform
+call on the same rectangle and against the same work as separate calls: a
+uniform chunk call over the sequences with count == q_max plus a decode call
+over those with count == 1 (sequences with count 0 cost nothing there).
+
+--pkg DIR imports kvecc from DIR instead of this tree (the same measurement on
+another build, e.g. the parent commit's, in the same session).
 """
 
 from __future__ import annotations
@@ -49,7 +59,12 @@ def main():
                          "bit errors at --ber (what a cache holds)")
     ap.add_argument("--ber", type=float, default=None, help="encoded data: BER (default 1e-3 H84, 1e-2 Golay)")
     ap.add_argument("--q-len", type=int, default=1, help="query tokens per sequence (1: one decode step)")
+    ap.add_argument("--only", choices=["chunk"], default=None, help="--q-len > 1: time the chunk call alone")
+    ap.add_argument("--q-spans", default=None, help="counts per sequence, right-aligned in --q-len tokens")
+    ap.add_argument("--pkg", default=None, help="directory to import kvecc from (default: this tree)")
     args = ap.parse_args()
+    if args.pkg:
+        sys.path.insert(0, os.path.abspath(args.pkg))
     from kvecc import ops
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -148,8 +163,44 @@ def main():
             mask = torch.arange(args.ctx, device=dev).view(1, 1, args.ctx) <= qpos
             return F.scaled_dot_product_attention(qc, k_t, v_t, attn_mask=mask.unsqueeze(1))
 
+        def entry(ms, passes):
+            return {"ms_per_call": ms, "pass_ms": [round(x, 5) for x in passes], "spread_ms": max(passes) - min(passes)}
+
+        if args.q_spans:
+            counts = [int(c) for c in args.q_spans.split(",")]
+            if len(counts) != args.batch or any(not 0 <= c <= n for c in counts):
+                raise SystemExit(f"--q-spans needs {args.batch} counts in [0, {n}]")
+            spans = ops.query_spans(counts, [n - c for c in counts], q_max=n, device=dev)
+            full = [b for b, c in enumerate(counts) if c == n]
+            ones = [b for b, c in enumerate(counts) if c == 1]
+
+            def ragged():
+                ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm, args.codec,
+                                               args.ctx, q_spans=spans)
+
+            res = {"ragged": entry(*timed(ragged)), "uniform": entry(*timed(chunk))}
+            if len(full) + len(ones) + counts.count(0) == args.batch:
+                total = 0.0
+                if full:
+                    qf, of = qt[full].contiguous(), torch.empty_like(outc[full])
+                    tf, lf = table[full].contiguous(), lens[full].contiguous()
+                    res["compact_chunk"] = entry(*timed(lambda: ops.paged_attention_chunk_into(
+                        qf, kc, vc, tf, lf, ks, vs, of, 0, args.bs, sm, args.codec, args.ctx)))
+                    total += res["compact_chunk"]["ms_per_call"]
+                if ones:
+                    qo, oo = qc[ones, :, n - 1].contiguous(), torch.empty_like(out[ones])
+                    to, lo = table[ones].contiguous(), lens[ones].contiguous()
+                    res["compact_decode"] = entry(*timed(lambda: ops.paged_attention_into(
+                        qo, kc, vc, to, lo, ks, vs, oo, 0, args.bs, sm, args.codec, args.ctx)))
+                    total += res["compact_decode"]["ms_per_call"]
+                res["compact_sum_ms"] = total
+            print(json.dumps({"kernel": "paged_attention_chunk_ragged", "codec": args.codec, "batch": args.batch,
+                              "q_max": n, "q_spans": counts, "heads": args.heads, "kv_heads": args.kv_heads,
+                              "head_dim": args.d, "ctx": args.ctx, **res, "data": data}))
+            return
         res = {}
-        for name, fn in (("chunk", chunk), ("decode_calls", decodes), ("read_sdpa", read_sdpa)):
+        every = (("chunk", chunk), ("decode_calls", decodes), ("read_sdpa", read_sdpa))
+        for name, fn in every[:1] if args.only == "chunk" else every:
             ms, passes = timed(fn)
             res[name] = {"ms_per_call": ms, "pass_ms": [round(x, 5) for x in passes],
                          "spread_ms": max(passes) - min(passes)}
