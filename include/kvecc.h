@@ -486,6 +486,50 @@ KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_ba
                                                  int64_t max_context_len, float sm_scale, int codec,
                                                  float *workspace, int64_t workspace_floats, void *stream);
 
+/* ---- Cache scrub --------------------------------------------------------------- */
+/* In-place patrol scrub of a resident paged cache (no reference counterpart:
+ * the reference's cache lives for one forward, and every reader here corrects
+ * into its output or its registers and leaves the codeword in HBM wrong).  ONE
+ * launch handles every codeword of every valid token of layers [layer_first,
+ * layer_first + layer_count) of every sequence, K and V alike: the word is
+ * decoded with the library's decoder and
+ *   - a CORRECTABLE word whose stored codeword bits differ from
+ *     encode(decoded data) is replaced by that codeword: H74 any non-zero
+ *     syndrome (doubles are miscorrected, as the decoder does); H84 a single
+ *     (type 1) or an overall-parity error (type 3); Golay 1 to 3 flipped bits,
+ *     parity bits with clean data included;
+ *   - an UNCORRECTABLE word (H84 double, type 2; Golay count 4) stays bit for
+ *     bit as it is -- the readers keep its data too;
+ *   - bits outside the codeword are neither examined nor changed: bit 7 of an
+ *     H74 byte, bits 24..31 of an int32 Golay word, the pad bytes of a packed
+ *     row.  Scales, slots at or beyond a sequence's length, layers outside the
+ *     range and blocks no table row names stay untouched;
+ *   - a clean word is not stored (a lane may store the whole 16-byte vector or
+ *     12-byte packed group it loaded when a word in it is dirty): a pass over a
+ *     clean cache writes nothing, and a second pass rewrites nothing.
+ * Caches as kvecc_shim_write ([blocks, num_layers, hkv, block_size, P]; codec
+ * H74, H84, GOLAY or GOLAY_PACKED -- KVECC_CODEC_NONE is KVECC_EINVAL, there is
+ * nothing to scrub), 4-byte aligned; d <= 512, d % 4 == 0 for the byte codecs.
+ * block_table is [batch, table_stride] device int32; context_lens is device
+ * int32 the host never reads: sequence b of layer l holds
+ * context_lens[(l - layer_first) * lens_layer_stride + b] tokens (stride 0: one
+ * row serves every layer), clamped to min(max_context_len, table_stride *
+ * block_size) as kvecc_paged_attention clamps (max_context_len <= 0: the table
+ * bound).  A length <= 0 skips the sequence, a block id < 0 or >= num_blocks
+ * the block: nothing is read and nothing written.  Two table rows may name the
+ * same block (both writers store the same value).  batch == 0 or layer_count
+ * == 0 enqueues nothing.
+ * stats (sharded buffer, may be NULL): stats[0] and stats[1] += what
+ * kvecc_shim_read adds for the codec (H74: flagged / 0; H84: single corrected /
+ * double detected; Golay: bits corrected / uncorrectable words), stats[2] +=
+ * words rewritten, stats[3] += words scanned. */
+KVECC_API int kvecc_cache_scrub(void *k_cache, void *v_cache, const int32_t *block_table,
+                                int64_t table_stride, const int32_t *context_lens,
+                                int64_t lens_layer_stride, int64_t batch, int64_t hkv, int64_t d,
+                                int64_t num_blocks, int64_t num_layers, int64_t layer_first,
+                                int64_t layer_count, int64_t block_size, int64_t max_context_len,
+                                int codec, uint64_t *stats, void *stream);
+
 /* ---- Host ("cpu") backend ------------------------------------------------- */
 /* The reference has no CPU codec backend (every wrapper asserts x.is_cuda,
  * e.g. hamming74_triton.py:185,246, golay_triton.py:399,456); BASELINE config 1 asks
@@ -582,6 +626,13 @@ KVECC_API int kvecc_cpu_shim_read_batch(const void *k_cache, const void *v_cache
                                         int64_t num_layers, int64_t block_size, int64_t layer,
                                         int codec, int interp, void *k_out, void *v_out,
                                         int out_dtype, uint64_t *stats, int threads);
+/* kvecc_cache_scrub on host pointers; stats[0..3] += into a plain host array */
+KVECC_API int kvecc_cpu_cache_scrub(void *k_cache, void *v_cache, const int32_t *block_table,
+                                    int64_t table_stride, const int32_t *context_lens,
+                                    int64_t lens_layer_stride, int64_t batch, int64_t hkv, int64_t d,
+                                    int64_t num_blocks, int64_t num_layers, int64_t layer_first,
+                                    int64_t layer_count, int64_t block_size, int64_t max_context_len,
+                                    int codec, uint64_t *stats, int threads);
 KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const void *k_cache,
                                         const void *v_cache, const int32_t *block_table,
                                         const int32_t *context_lens, const float *k_scales,

@@ -417,4 +417,71 @@ KV_HD uint32_t interp_word(uint32_t q, uint32_t l, uint32_t r, uint32_t e) {
   return sat15((avg_up(l, r) & m) | (q & ~m));
 }
 
+// ---- cache scrub: a stored codeword -> the codeword to store back -------------
+// (scrub.hip and its host twin in cpu.hip).  Each function returns the XOR of
+// the stored word and the word to store: 0 = clean or uncorrectable, nothing to
+// write.  Bits outside the codeword are never set in the result.
+
+// number of non-zero bytes of a word
+KV_HD uint32_t nonzero_bytes4(uint32_t x) {
+  x |= x >> 4;
+  x |= x >> 2;
+  x |= x >> 1;
+  return (uint32_t)__builtin_popcount(x & 0x01010101u);
+}
+
+// The cheap first look of a scrub pass: non-zero iff one of the four bytes is not
+// a valid codeword (H84: syndrome or overall parity; H74: syndrome of bits 0..6)
+KV_HD uint32_t h84_dirty4(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return h_code4(w);
+#else
+  return HammingSyndrome(w).nz | byte_parity4(w);
+#endif
+}
+KV_HD uint32_t h74_dirty4(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return h_code4(w) & 0x07070707u;
+#else
+  return HammingSyndrome(w).nz;
+#endif
+}
+// ... and of a Golay codeword: its 12-bit syndrome, 0 iff bits 0..23 are a codeword
+KV_HD uint32_t golay_syndrome1(uint32_t w, const uint16_t *par) {
+  return ((w >> 12) & 0xFFFu) ^ par[w & 0xFFFu];
+}
+
+// four Hamming(8,4) codewords: singles (type 1) and overall-parity errors (type
+// 3) become encode(decoded data); doubles (type 2) stay as they are
+KV_HD uint32_t h84_scrub4(uint32_t w, uint32_t &n_single, uint32_t &n_double, uint32_t &n_rewritten) {
+  uint32_t data, type;
+  h84_decode4(w, data, type, n_single, n_double);
+  const uint32_t x = (h84_encode4(data) ^ w) & ~is_double(type);
+  n_rewritten += nonzero_bytes4(x);
+  return x;
+}
+
+// four Hamming(7,4) codewords: any non-zero syndrome is "corrected" (doubles are
+// miscorrected, as the decoder does); bit 7 of each byte is not part of the code
+KV_HD uint32_t h74_scrub4(uint32_t w, uint32_t &n_flag, uint32_t &n_rewritten) {
+  uint32_t data, flag;
+  h74_decode4(w, data, flag, n_flag);
+  const uint32_t x = (h74_encode4(data) ^ w) & 0x7F7F7F7Fu;
+  n_rewritten += nonzero_bytes4(x);
+  return x;
+}
+
+// one Golay(24,12) codeword in bits 0..23 of w (higher bits ignored): up to 3
+// flipped bits, data or parity, become encode(decoded data); c == 4 stays
+KV_HD uint32_t golay_scrub1(uint32_t w, const uint16_t *par, const uint16_t *cor, uint32_t &n_bits,
+                            uint32_t &n_unc, uint32_t &n_rewritten) {
+  uint32_t c;
+  const uint32_t d = golay_decode1(w, par, cor, c);
+  n_bits += c & 3u;
+  n_unc += c >> 2;
+  const uint32_t x = c >= 4 ? 0u : ((d | (uint32_t)par[d] << 12) ^ w) & 0xFFFFFFu;
+  n_rewritten += x != 0;
+  return x;
+}
+
 }  // namespace kvecc

@@ -900,6 +900,108 @@ KVECC_API int kvecc_cpu_shim_read_batch(const void *k_cache, const void *v_cache
   return KVECC_OK;
 }
 
+// host twin of kvecc_cache_scrub (scrub.hip): the same segments, skip rules and
+// per-word functions (codec_math.h *_scrub*), one (sequence, layer, block, side)
+// at a time; statistics 0..3 into a plain host array
+KVECC_API int kvecc_cpu_cache_scrub(void *k_cache, void *v_cache, const int32_t *block_table,
+                                    int64_t table_stride, const int32_t *context_lens,
+                                    int64_t lens_layer_stride, int64_t batch, int64_t hkv, int64_t d,
+                                    int64_t num_blocks, int64_t num_layers, int64_t layer_first,
+                                    int64_t layer_count, int64_t block_size, int64_t max_context_len,
+                                    int codec, uint64_t *stats, int threads) {
+  if (table_stride < 0 || lens_layer_stride < 0 || batch < 0 || hkv < 0 || d < 0 || num_blocks < 0 ||
+      num_layers < 0 || layer_first < 0 || layer_count < 0 || block_size < 0)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: negative size");
+  if (codec == KVECC_CODEC_NONE)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: codec none has nothing to scrub");
+  if (codec < KVECC_CODEC_NONE || codec > KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: bad codec %d", codec);
+  if (batch == 0 || layer_count == 0 || hkv == 0) return KVECC_OK;
+  const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
+  const bool golay = codec == KVECC_CODEC_GOLAY || packed;
+  if (d < 1 || d > 512)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: head_dim %lld not in [1, 512]", (long long)d);
+  if (!golay && d % 4 != 0)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: head_dim %lld must be a multiple of 4", (long long)d);
+  if (num_layers < 1 || block_size < 1 || num_blocks < 1 || layer_first + layer_count > num_layers)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: bad cache geometry (layers [%lld, %lld) of %lld)",
+                     (long long)layer_first, (long long)(layer_first + layer_count), (long long)num_layers);
+  if (table_stride < 1)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: table stride %lld < 1", (long long)table_stride);
+  if (!k_cache || !v_cache || !block_table || !context_lens)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: null pointer");
+  if (table_stride > 0x7FFFFFFFLL || block_size > 0x7FFFFFFFLL || table_stride * block_size > 0x7FFFFFFFLL ||
+      batch > 0x7FFFFFFFLL || layer_count > 0x7FFFFFFFLL)
+    return set_error(KVECC_EINVAL, "cpu_cache_scrub: sizes exceed 32-bit indexing");
+  static uint16_t tab[8192];
+  static bool ready = [] {
+    build_golay_parity_table(tab);
+    build_golay_correct_table(tab + 4096);
+    return true;
+  }();
+  (void)ready;
+  const int64_t g = golay ? (d + 2) / 3 : d;
+  const int64_t rowb = packed ? KVECC_GOLAY_PACKED_ROW(g) : golay ? 4 * g : d;
+  int64_t bound = table_stride * block_size;
+  if (max_context_len > 0 && max_context_len < bound) bound = max_context_len;
+  const int64_t nlb = (bound + block_size - 1) / block_size;
+  const int64_t nseg = 2 * batch * layer_count * nlb;
+  struct Acc4 {
+    uint64_t v[4] = {0, 0, 0, 0};
+    char pad[32];
+  };
+  std::vector<Acc4> acc(std::max(1, clamp_threads(threads, nseg, 1)));
+  parallel_for(nseg, threads, 1, [&](int64_t s0, int64_t s1, int t) {
+    uint32_t c0 = 0, c1 = 0, rew = 0;  // per run of one head (< 2^31 codewords), summed into acc
+    for (int64_t s = s0; s < s1; ++s) {
+      const int64_t side = s & 1, q = s >> 1;
+      const int64_t lb = q % nlb, bl = q / nlb;
+      const int64_t li = bl % layer_count, b = bl / layer_count;
+      const int64_t len = std::min<int64_t>(context_lens[li * lens_layer_stride + b], bound);
+      const int64_t nv = std::min<int64_t>(block_size, len - lb * block_size);
+      if (nv <= 0) continue;
+      const int64_t blk = block_table[b * table_stride + lb];
+      if (blk < 0 || blk >= num_blocks) continue;
+      uint8_t *base = reinterpret_cast<uint8_t *>(side ? v_cache : k_cache) +
+                      ((blk * num_layers + layer_first + li) * hkv) * block_size * rowb;
+      for (int64_t h = 0; h < hkv; ++h) {
+        uint8_t *run = base + h * block_size * rowb;
+        c0 = c1 = rew = 0;
+        if (packed) {
+          for (int64_t r = 0; r < nv; ++r)
+            for (int64_t k = 0; k < g; ++k) {
+              uint8_t *c = run + r * rowb + 3 * k;
+              const uint32_t w = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+              const uint32_t x = golay_scrub1(w, tab, tab + 4096, c0, c1, rew);
+              if (x) {  // whole bytes of the canonical word: a second writer of a shared block stores the same
+                c[0] = (uint8_t)(w ^ x);
+                c[1] = (uint8_t)((w ^ x) >> 8);
+                c[2] = (uint8_t)((w ^ x) >> 16);
+              }
+            }
+          acc[t].v[3] += (uint64_t)(nv * g);
+        } else {
+          for (int64_t i = 0; i < nv * rowb; i += 4) {
+            const uint32_t w = load4(run + i);
+            const uint32_t x = codec == KVECC_CODEC_H84   ? h84_scrub4(w, c0, c1, rew)
+                               : codec == KVECC_CODEC_H74 ? h74_scrub4(w, c0, rew)
+                                                          : golay_scrub1(w, tab, tab + 4096, c0, c1, rew);
+            if (x) store4(run + i, w ^ x);
+          }
+          acc[t].v[3] += (uint64_t)(nv * g);
+        }
+        acc[t].v[0] += c0;
+        acc[t].v[1] += c1;
+        acc[t].v[2] += rew;
+      }
+    }
+  });
+  if (stats)
+    for (auto &x : acc)
+      for (int k = 0; k < 4; ++k) stats[k] += x.v[k];
+  return KVECC_OK;
+}
+
 // ---- paged decode attention (host twin of attention.hip) ---------------------
 // The reference's order exactly: one (b, h) at a time, tokens in order, online
 // softmax in fp32 (attention_ecc.py:355-427).  No valid token: Hamming(8,4)

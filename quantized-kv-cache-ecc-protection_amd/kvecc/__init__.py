@@ -14,7 +14,7 @@ from .config import (DecodeResult, ErrorType, FAULT_INJECTION_BLOCK_SIZE, GOLAY_
                      INTERPOLATION_BLOCK_SIZE, SYNDROME_LUT_HAMMING74, SYNDROME_LUT_HAMMING84,
                      build_golay_syndrome_table, get_codeword_bits, get_data_bits,
                      get_physical_dtype)
-from .ops import (fused_decode_dequantize_hamming84, fused_quantize_encode_hamming74,
+from .ops import (cache_scrub, fused_decode_dequantize_hamming84, fused_quantize_encode_hamming74,
                   fused_quantize_encode_hamming84, golay_decode, golay_encode, hamming74_decode,
                   hamming74_encode, hamming84_decode, hamming84_encode, inject_bit_errors,
                   inject_bit_errors_triton, inject_bit_errors_triton_batched,
@@ -26,7 +26,7 @@ from . import torch_ops  # noqa: F401  -- registers torch.ops.kvecc.* (CPU + HIP
 __version__ = "0.1.0"
 
 __all__ = [
-    "paged_attention_ecc", "paged_attention_chunk", "query_spans", "query_spans_from_mask",
+    "paged_attention_ecc", "paged_attention_chunk", "query_spans", "query_spans_from_mask", "cache_scrub",
     "get_physical_dtype", "get_codeword_bits", "get_data_bits",
     "HAMMING74_BLOCK_SIZE", "HAMMING84_BLOCK_SIZE", "GOLAY_BLOCK_SIZE",
     "FAULT_INJECTION_BLOCK_SIZE", "INTERPOLATION_BLOCK_SIZE",

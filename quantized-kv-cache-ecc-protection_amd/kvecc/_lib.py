@@ -76,6 +76,10 @@ SIGNATURES = {
     "kvecc_paged_attention_chunk_ragged": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                            _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
                                            _vp, _i64, _vp],
+    "kvecc_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                          _int, _vp, _vp],
+    "kvecc_cpu_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                              _int, _vp, _int],
     # host backend (threads instead of a stream)
     "kvecc_cpu_hamming74_encode": [_vp, _vp, _i64, _int],
     "kvecc_cpu_hamming84_encode": [_vp, _vp, _i64, _int],

@@ -26,6 +26,11 @@ FUNCTIONS = (
     "fused_decode_dequantize_hamming84",
 )
 
+# Native extensions beyond the reference's set that the two built-in backends
+# ("hip", "cpu") both provide; a registered third-party backend may lack them
+# (the shim then raises where it needs one): the in-place cache scrub.
+NATIVE_FUNCTIONS = ("cache_scrub_tensors",)
+
 # backend name -> module implementing FUNCTIONS
 CODEC_BACKENDS = {
     "hip": "kvecc.ops",
@@ -55,6 +60,8 @@ def get_codec_backend(backend: str = DEFAULT_BACKEND) -> types.ModuleType:
                          f"Available backends: {', '.join(CODEC_BACKENDS)}")
     mod = importlib.import_module(CODEC_BACKENDS[key])
     missing = [f for f in FUNCTIONS if not hasattr(mod, f)]
+    if key in ("hip", "cpu"):
+        missing += [f for f in NATIVE_FUNCTIONS if not hasattr(mod, f)]
     if missing:
         raise ValueError(f"codec backend '{backend}' lacks {missing}")
     if key == "hip":

@@ -539,6 +539,39 @@ def shim_append_ragged_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block
               int(num_layers), int(block_size), int(layer), NUM_THREADS)
 
 
+def new_scrub_stats(device=None):
+    """Host statistics buffer of cache_scrub_tensors: int64 [4] (corrected,
+    detected, rewritten, scanned)."""
+    return torch.zeros(4, dtype=torch.int64)
+
+
+def check_scrub_stats(stats, device=None):
+    """A scrub statistics buffer is a contiguous host int64 tensor of >= 4 elements."""
+    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
+            or stats.numel() < 4 or stats.device.type != "cpu"):
+        raise ValueError("scrub stats must be a contiguous int64 host tensor of >= 4 elements "
+                         f"(cpu_ops.new_scrub_stats), got {getattr(stats, 'dtype', type(stats))} "
+                         f"{tuple(getattr(stats, 'shape', ()))} on {getattr(stats, 'device', None)}")
+
+
+def cache_scrub_tensors(k_cache, v_cache, block_table, context_lens, head_dim, block_size, num_layers, codec,
+                        layer_first=0, layer_count=None, max_context_len=0, stats=None):
+    """Host twin of ops.cache_scrub_tensors (kvecc_cpu_cache_scrub): same
+    arguments, rules and statistics; ``stats`` is a host int64 [>= 4]."""
+    from .ops import _check_cache_scrub_args  # pure torch, device-agnostic
+    if k_cache.device.type != "cpu":
+        raise ValueError(f"the cpu backend scrubs host tensors, k_cache is on {k_cache.device}")
+    layer_count = int(num_layers) - int(layer_first) if layer_count is None else layer_count
+    batch, hkv, nb, stride = _check_cache_scrub_args(k_cache, v_cache, block_table, context_lens, head_dim,
+                                                     block_size, num_layers, codec, layer_first, layer_count)
+    if stats is not None:
+        check_scrub_stats(stats)
+    _lib.call("kvecc_cpu_cache_scrub", _ptr(k_cache), _ptr(v_cache), _ptr(block_table), block_table.shape[1],
+              _ptr(context_lens), stride, batch, hkv, int(head_dim), nb, int(num_layers), int(layer_first),
+              int(layer_count), int(block_size), int(max_context_len or 0), SHIM_CODECS[codec], _ptr(stats),
+              NUM_THREADS)
+
+
 def shim_read(manager, layer, ctx, codec, interp, out_dtype, stats=None, seq_id=0):
     return shim_read_tensors(manager.k_cache, manager.v_cache, manager.k_scales, manager.v_scales,
                              manager.block_table[seq_id], ctx, manager.num_kv_heads, manager.head_dim,

@@ -117,6 +117,8 @@ class ECCShimConfig:
     MHA and 4 query heads per cache head: profiles/chunk_attention/); fp32 and
     bf16 models and other head_dims run the split kernels once per query row,
     which re-decode the cache for each and have not been measured.
+    The error counts those paths do not keep are a by-product of
+    scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
 
     SUPPORTED_CODECS = {"fp16", "fp8", "int4", "hamming74", "hamming84", "golay"}
@@ -324,6 +326,10 @@ class SimpleBlockManager:
         return cache.view(self.num_blocks, self.num_layers, self.num_kv_heads, self.block_size, -1)
 
 
+# age_ecc_cache draws V's flips with seed + V_SEED_OFFSET: consecutive seeds (one
+# per round of an experiment) then never give K of one round V's draw of another
+V_SEED_OFFSET = 1_000_003
+
 _N_BITS = {"hamming74": 7, "hamming84": 8, "golay": 24, "int4": 4, "fp8": 8}
 
 
@@ -358,6 +364,10 @@ class ECCBackend:
         self._injection_count = 0
         self._total_values = 0
         self._stats = self.codec_backend.new_stats(manager.k_cache.device)  # backend counters
+        # cumulative counters of scrub() alone (corrected, detected, rewritten,
+        # scanned), allocated by the first scrub; get_ecc_stats never reads them
+        self._scrub_stats = None
+        self._scrub_len = {}  # overwrite mode: context length -> its one-element device tensor
         # ragged batches (set_query_spans): host (counts, firsts) and the
         # persistent device buffer [max_seqs, 3] the kernels read
         self._spans = None
@@ -376,6 +386,90 @@ class ECCBackend:
         self._injection_count = 0
         self._total_values = 0
         self._stats.zero_()
+        if self._scrub_stats is not None:
+            self._scrub_stats.zero_()
+
+    # ---- cache scrub (no reference counterpart) -----------------------------------
+    SCRUB_CODECS = ("hamming74", "hamming84", "golay")
+
+    def _layer_runs(self, layers):
+        """Runs (first, count) of consecutive layers covering `layers` (None: all)."""
+        n = self.manager.num_layers
+        if layers is None:
+            return [(0, n)]
+        ls = sorted({int(x) for x in ([layers] if isinstance(layers, int) else layers)})
+        if any(not 0 <= x < n for x in ls):
+            raise ValueError(f"layers {ls} outside the cache's {n} layers")
+        runs = []
+        for x in ls:
+            if runs and runs[-1][0] + runs[-1][1] == x:
+                runs[-1][1] += 1
+            else:
+                runs.append([x, 1])
+        return [tuple(r) for r in runs]
+
+    def scrub(self, layers=None):
+        """Correct and re-encode the resident codewords of `layers` (None: every
+        layer) in place, all live sequences in one launch (one per run of
+        consecutive layers): a correctable word that differs from
+        encode(decoded data) is rewritten, so errors stop piling up in a cache
+        that stays resident for a whole generation.  Append mode scrubs every
+        sequence up to its own per-layer length, overwrite mode sequence 0.
+        Counts add into a scrub-only buffer (scrub_totals()); the decode
+        statistics of get_ecc_stats are not touched.  Nothing is read back, so
+        the call can be captured in a HIP graph between forwards."""
+        cfg, mgr = self.config, self.manager
+        if cfg.codec not in self.SCRUB_CODECS:
+            raise ValueError(f"codec {cfg.codec!r} has no ECC: nothing to scrub (one of {self.SCRUB_CODECS})")
+        be = self.codec_backend
+        if not hasattr(be, "cache_scrub_tensors"):
+            raise ValueError("this backend has no cache scrub (cache_scrub_tensors)")
+        if self._scrub_stats is None:
+            self._scrub_stats = be.new_scrub_stats(mgr.k_cache.device)
+        fn = self._scrub_op if self._traced() else be.cache_scrub_tensors
+        for first, count in self._layer_runs(layers):
+            if self.append:
+                batch = max(mgr.seq_to_blocks, default=-1) + 1  # sequences are 0 .. batch-1
+                if batch == 0:
+                    continue
+                mcl = max(max(mgr.layer_lens(l, batch)) for l in range(first, first + count))
+                if mcl == 0:
+                    continue
+                fn(mgr.k_cache, mgr.v_cache, mgr.block_table[:batch], mgr.ctx_lens[first:first + count],
+                   self.head_dim, mgr.block_size, mgr.num_layers, mgr.shim_codec, first, count, mcl,
+                   self._scrub_stats)
+            else:
+                n = mgr.get_context_len(0)
+                if n == 0:
+                    continue
+                lens = self._scrub_len.get(n)
+                if lens is None:  # a device fill, no host-to-device copy
+                    lens = self._scrub_len[n] = torch.full((1,), n, dtype=torch.int32, device=mgr.k_cache.device)
+                fn(mgr.k_cache, mgr.v_cache, mgr.block_table[0:1], lens, self.head_dim, mgr.block_size,
+                   mgr.num_layers, mgr.shim_codec, first, count, n, self._scrub_stats)
+
+    @staticmethod
+    def _scrub_op(*args):
+        torch.ops.kvecc.cache_scrub(*args)
+
+    def scrub_totals(self):
+        """Device int64 [4] of the cumulative scrub counters (corrected, detected,
+        rewritten, scanned) since the last reset; no host sync."""
+        if self._scrub_stats is None:
+            return torch.zeros(4, dtype=torch.int64, device=self.manager.k_cache.device)
+        return self.codec_backend.stats_totals(self._scrub_stats, 4)
+
+    def age(self, ber, seed):
+        """Residency-error model: in-place Bernoulli flips over the WHOLE K and V
+        cache tensors (V with seed + V_SEED_OFFSET); see age_ecc_cache."""
+        cfg, mgr = self.config, self.manager
+        if cfg.codec not in self.SCRUB_CODECS:
+            raise ValueError(f"codec {cfg.codec!r} has no ECC cache to age (one of {self.SCRUB_CODECS})")
+        if not ber > 0:
+            return
+        n_bits = 8 if mgr.golay_packed else _N_BITS[cfg.codec]
+        for i, cache in enumerate((mgr.k_cache, mgr.v_cache)):
+            torch.ops.kvecc.inject_bit_errors_(cache, float(ber), n_bits, int(seed) + i * V_SEED_OFFSET)
 
     def _inject_rows(self, enc, rows, row_len, seed_base):
         """Per-row injection of the reference's write loop, in place."""
@@ -1032,3 +1126,37 @@ def get_ecc_stats(model):
         stats["errors_detected"] = detected
         stats["total_values"] = be._total_values
     return stats
+
+
+_SCRUB_KEYS = ("corrected", "detected", "rewritten", "scanned")
+
+
+def scrub_ecc_cache(model, layers=None):
+    """Scrub the patched model's resident KV cache in place (no reference
+    counterpart; ECCBackend.scrub): every correctable codeword of the cached
+    tokens of `layers` (None: all) that differs from its canonical form is
+    rewritten, uncorrectable words stay.  Call it between forwards.  Returns this
+    call's {"corrected", "detected", "rewritten", "scanned"} (per-codec meaning
+    of the first two as get_ecc_stats' errors_corrected / errors_detected; one
+    device sync); the counts also add into cumulative scrub counters that
+    reset_ecc_cache clears and get_ecc_stats does not include."""
+    if not hasattr(model, "_ecc_backend"):
+        raise ValueError("model is not patched with patch_model_with_ecc_attention")
+    be = model._ecc_backend
+    before = be.scrub_totals()
+    be.scrub(layers)
+    return dict(zip(_SCRUB_KEYS, (int(x) for x in (be.scrub_totals() - before).tolist())))
+
+
+def age_ecc_cache(model, ber, seed):
+    """Residency-error model for experiments ("BER p per step, scrub every k
+    steps"): flip every bit of the resident K and V cache tensors with
+    probability `ber`, in place, with the library's in-place injection (K with
+    `seed`, V with `seed + V_SEED_OFFSET`; 7 / 8 / 24 bits per element for hamming74 /
+    hamming84 / golay, 8 per byte of the packed Golay layout).  The WHOLE cache
+    tensors are aged: unused slots, free blocks and the pad bytes of packed rows
+    are flipped too (bit 7 of a hamming74 byte and bits 24..31 of an int32 Golay
+    word are not).  The fp32 scales are not touched."""
+    if not hasattr(model, "_ecc_backend"):
+        raise ValueError("model is not patched with patch_model_with_ecc_attention")
+    model._ecc_backend.age(ber, seed)

@@ -945,6 +945,133 @@ def shim_read_batch(k_cache, v_cache, k_scales, v_scales, block_table, ctx, head
 
 
 # ============================================================================
+# Cache scrub: correct and re-encode resident codewords in place
+# ============================================================================
+
+SCRUB_CODECS = ("hamming74", "hamming84", "golay", "golay_packed")
+SCRUB_STATS = ("corrected", "detected", "rewritten", "scanned")
+
+
+def _check_cache_scrub_args(k_cache, v_cache, block_table, context_lens, head_dim, block_size, num_layers, codec,
+                            layer_first, layer_count):
+    """Validate a scrub (both backends) before anything is touched: codec, cache
+    dtype and [blocks, num_layers, hkv, block_size * P] geometry, the layer
+    range, block_table int32 [batch, n], context_lens int32 [batch] (one row for
+    every layer) or [layer_count, >= batch] (row i = layer layer_first + i),
+    contiguity, one device.  A mismatch raises ValueError.
+    Returns (batch, hkv, num_blocks, lens_layer_stride)."""
+    if codec not in SCRUB_CODECS:
+        raise ValueError(f"cache scrub codec {codec!r}: one of {SCRUB_CODECS} (a codec without ECC has "
+                         "nothing to scrub)")
+    head_dim, block_size, num_layers = int(head_dim), int(block_size), int(num_layers)
+    if not 1 <= head_dim <= 512 or (codec in ("hamming74", "hamming84") and head_dim % 4):
+        raise ValueError(f"head_dim {head_dim} must be in [1, 512] and a multiple of 4 for the byte codecs")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
+    nb, nl, hkv, row = k_cache.shape
+    for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if c.dtype != _SHIM_CACHE_DT[codec]:
+            raise ValueError(f"{codec} {name} must be {_SHIM_CACHE_DT[codec]}, got {c.dtype}")
+    per = {"golay": (head_dim + 2) // 3, "golay_packed": (3 * ((head_dim + 2) // 3) + 3) // 4 * 4}.get(
+        codec, head_dim)
+    if block_size < 1 or nl != num_layers or row != block_size * per:
+        raise ValueError(f"{codec} caches must be [blocks, {num_layers}, kv_heads, {block_size}*{per}], got "
+                         f"{tuple(k_cache.shape)}")
+    layer_first, layer_count = int(layer_first), int(layer_count)
+    if layer_first < 0 or layer_count < 0 or layer_first + layer_count > num_layers:
+        raise ValueError(f"layers [{layer_first}, {layer_first + layer_count}) outside the cache's {num_layers}")
+    if block_table.dim() != 2 or block_table.dtype != torch.int32 or block_table.shape[1] < 1:
+        raise ValueError("block_table must be a contiguous int32 [batch, max_blocks] tensor")
+    batch = block_table.shape[0]
+    if context_lens.dtype != torch.int32 or context_lens.dim() not in (1, 2):
+        raise ValueError(f"context_lens must be int32 [batch] or [layers, batch], got {context_lens.dtype} "
+                         f"{tuple(context_lens.shape)}")
+    if context_lens.dim() == 1:
+        if context_lens.shape[0] != batch:
+            raise ValueError(f"context_lens {tuple(context_lens.shape)} does not hold a batch of {batch}")
+        stride = 0
+    else:
+        if context_lens.shape[0] < layer_count or context_lens.shape[1] < batch:
+            raise ValueError(f"context_lens {tuple(context_lens.shape)} does not hold {layer_count} layers of "
+                             f"a batch of {batch}")
+        stride = context_lens.shape[1]
+    for name, t in (("v_cache", v_cache), ("block_table", block_table), ("context_lens", context_lens)):
+        if t.device != k_cache.device:
+            raise ValueError(f"{name} is on {t.device}, k_cache on {k_cache.device}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache), ("block_table", block_table),
+                    ("context_lens", context_lens)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return batch, hkv, nb, stride
+
+
+def cache_scrub_tensors(k_cache, v_cache, block_table, context_lens, head_dim, block_size, num_layers, codec,
+                        layer_first=0, layer_count=None, max_context_len=0, stats=None):
+    """In-place scrub of a paged cache (kvecc_cache_scrub, one launch): every
+    correctable codeword of the valid tokens of layers [layer_first, layer_first
+    + layer_count) that differs from encode(decoded data) is rewritten,
+    uncorrectable words and everything outside the codewords stay.  block_table
+    int32 [batch, n]; context_lens int32 [batch] or [layer_count, >= batch] on
+    the device, never read by the host.  ``stats`` (ops.new_stats) accumulates
+    statistics 0..3: corrected, detected, rewritten, scanned."""
+    if not k_cache.is_cuda:
+        raise ValueError(f"the hip backend scrubs GPU tensors, k_cache is on {k_cache.device}")
+    layer_count = int(num_layers) - int(layer_first) if layer_count is None else layer_count
+    batch, hkv, nb, stride = _check_cache_scrub_args(k_cache, v_cache, block_table, context_lens, head_dim,
+                                                     block_size, num_layers, codec, layer_first, layer_count)
+    _ensure_device(k_cache.device)
+    _lib.call("kvecc_cache_scrub", _ptr(k_cache), _ptr(v_cache), _ptr(block_table), block_table.shape[1],
+              _ptr(context_lens), stride, batch, hkv, int(head_dim), nb, int(num_layers), int(layer_first),
+              int(layer_count), int(block_size), int(max_context_len or 0), SHIM_CODECS[codec],
+              _sptr(stats, k_cache.device), _stream(k_cache.device))
+
+
+def _layer_range(layers, num_layers):
+    """(first, count) of ``layers``: None = every layer, an int = that layer, or
+    a range / sequence of consecutive ascending layers."""
+    if layers is None:
+        return 0, int(num_layers)
+    if isinstance(layers, int):
+        return layers, 1
+    ls = [int(x) for x in layers]
+    if not ls:
+        return 0, 0
+    if ls != list(range(ls[0], ls[0] + len(ls))):
+        raise ValueError(f"layers must be consecutive and ascending, got {ls}")
+    return ls[0], len(ls)
+
+
+def cache_scrub(k_cache, v_cache, block_table, context_lens, *, head_dim, block_size, num_layers, codec,
+                layers=None, max_context_len=None, stats=None):
+    """Scrub a resident paged KV cache in place (GPU tensors: kvecc_cache_scrub;
+    host tensors: the host twin) and return the call's statistics as a device
+    int64 [4] -- corrected, detected, rewritten, scanned (SCRUB_STATS) -- with no
+    host sync.  ``layers``: None (all), an int, or consecutive layers;
+    ``stats``: a statistics buffer of the backend that also accumulates them."""
+    if k_cache.device.type == "cpu":
+        from . import cpu_ops as be
+    else:
+        from . import ops as be
+    first, count = _layer_range(layers, num_layers)
+    st = be.new_scrub_stats(k_cache.device)
+    be.cache_scrub_tensors(k_cache, v_cache, block_table, context_lens, head_dim, block_size, num_layers, codec,
+                           layer_first=first, layer_count=count, max_context_len=max_context_len or 0, stats=st)
+    if stats is not None:
+        be.check_scrub_stats(stats, k_cache.device)
+        stats[:st.numel()].add_(st)
+    return be.stats_totals(st, 4)
+
+
+def new_scrub_stats(device):
+    """A statistics buffer for cache_scrub_tensors (the sharded buffer of every kernel)."""
+    return new_stats(device)
+
+
+def check_scrub_stats(stats, device):
+    _sptr(stats, device)
+
+
+# ============================================================================
 # Paged decode attention with inline ECC decode
 # ============================================================================
 

@@ -341,6 +341,23 @@ def _(k_cache, v_cache, k_scales, v_scales, table, ctx, hkv, d, num_layers, bloc
     return k_cache.new_empty(shape, dtype=out_dtype), k_cache.new_empty(shape, dtype=out_dtype)
 
 
+@torch.library.custom_op("kvecc::cache_scrub", mutates_args=("k_cache", "v_cache", "stats"), device_types=_DEV)
+def cache_scrub(k_cache: Tensor, v_cache: Tensor, block_table: Tensor, context_lens: Tensor, head_dim: int,
+                block_size: int, num_layers: int, codec: str, layer_first: int, layer_count: int,
+                max_context_len: int, stats: Optional[Tensor]) -> None:
+    """In-place scrub of layers [layer_first, layer_first + layer_count) of a paged
+    cache (kvecc_cache_scrub; no reference counterpart); statistics 0..3
+    (corrected, detected, rewritten, scanned) accumulate into `stats`."""
+    _be(k_cache).cache_scrub_tensors(k_cache, v_cache, block_table, context_lens, head_dim, block_size,
+                                     num_layers, codec, layer_first, layer_count, max_context_len, stats)
+
+
+@cache_scrub.register_fake
+def _(k_cache, v_cache, block_table, context_lens, head_dim, block_size, num_layers, codec, layer_first,
+      layer_count, max_context_len, stats):
+    return None
+
+
 @torch.library.custom_op("kvecc::paged_attention", mutates_args=(), device_types=_DEV)
 def paged_attention(query: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor,
                     context_lens: Tensor, k_scales: Tensor, v_scales: Tensor, layer_idx: int, block_size: int,
@@ -402,6 +419,6 @@ OPS: List[str] = ["hamming74_encode", "hamming84_encode", "hamming74_decode", "h
                   "golay_encode", "golay_decode", "golay_encode_rows", "golay_decode_rows",
                   "inject_bit_errors", "inject_bit_errors_", "interpolate_double_errors",
                   "fused_quantize_encode", "fused_decode_dequantize_hamming84", "shim_write", "shim_append",
-                  "shim_append_ragged", "shim_read", "paged_attention", "paged_attention_chunk",
+                  "shim_append_ragged", "shim_read", "cache_scrub", "paged_attention", "paged_attention_chunk",
                   "paged_attention_chunk_ragged"]
 _ = _lib  # the operators bind libkvecc.so lazily, on first call

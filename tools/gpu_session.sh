@@ -17,6 +17,8 @@
 #   configs   tools/bench_configs.py (every BASELINE config's kernels)
 #   shim      tools/bench_shim.py: config 4 eager, HIP graph, inductor; host backend
 #   attn      tools/bench_attention.py, MHA and GQA, every codec
+#   scrub     tools/bench_scrub.py (clean / dirty scrub pass against shim_read_batch; profiles/scrub/)
+#             and tools/kernel_resources.py of the scrub kernels
 #   fuzz40    the geometry sweep + GPU fuzz at 40x (KVECC_SWEEP_SCALE), seed $SEED
 #   ipe       tools/exp/run_interp_read_exp.py (interpolating read A/B)
 #   gread     tools/exp/run_golay_read_exp.py $GREAD (fused Golay read A/B)
@@ -92,6 +94,8 @@ for s in $STEPS; do
              run attn_gqa 300 python tools/bench_attention.py --codec hamming84 --kv-heads 8
              run attn_gqa_golay 300 python tools/bench_attention.py --codec golay --kv-heads 8
              run attn_gqa_pk 300 python tools/bench_attention.py --codec golay_packed --kv-heads 8 ;;
+    scrub)   run bench_scrub 900 python tools/bench_scrub.py
+             run scrub_kernel_resources 120 python tools/kernel_resources.py cache_scrub ;;
     fuzz40)  KVECC_SWEEP_SCALE=40 KVECC_SWEEP_SEED=${SEED:-8} run pytest_sweep40 1400 $PYT \
                tests/test_geometry_sweep.py tests/test_shim_read_batch.py tests/test_gpu_fuzz.py -m gpu -v ;;
     ipe)     run ipe 300 python tools/exp/run_interp_read_exp.py ${IPE:-} ;;
