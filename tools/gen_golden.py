@@ -16,6 +16,7 @@ Usage (``-O`` strips the reference wrappers' ``assert x.is_cuda``)::
 from __future__ import annotations
 
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -331,6 +332,192 @@ def gen_shim_fp16(manifest):
                                        "dtype": "float16"}, **arrays)
 
 
+@contextlib.contextmanager
+def _record_shim(es):
+    """Record what the reference's ECCBackend is given and hands on, per call:
+    write -> (layer, k, v); _run_attention -> (layer, k_float, v_float), the
+    dequantized K/V of the Python path; and for an attend that never reaches
+    _run_attention (the seq_len == 1 Hamming(8,4) kernel path) -> (layer, q, out)."""
+    rec = {"write": [], "kv": [], "fast": []}
+    cur = {}
+    w0, r0, a0 = es.ECCBackend.write, es.ECCBackend._run_attention, es.ECCBackend.attend
+
+    def write(self, k, v, layer_idx, seq_id=0):
+        rec["write"].append((layer_idx, k.detach().clone(), v.detach().clone()))
+        return w0(self, k, v, layer_idx, seq_id)
+
+    def run_attention(self, q, k_float, v_float, device):
+        rec["kv"].append((cur["layer"], k_float.detach().clone(), v_float.detach().clone()))
+        return r0(self, q, k_float, v_float, device)
+
+    def attend(self, q, layer_idx, seq_id=0):
+        cur["layer"] = layer_idx
+        n = len(rec["kv"])
+        out = a0(self, q, layer_idx, seq_id)
+        if len(rec["kv"]) == n:
+            rec["fast"].append((layer_idx, q.detach().clone(), out.detach().clone()))
+        return out
+
+    es.ECCBackend.write, es.ECCBackend._run_attention, es.ECCBackend.attend = write, run_attention, attend
+    try:
+        yield rec
+    finally:
+        es.ECCBackend.write, es.ECCBackend._run_attention, es.ECCBackend.attend = w0, r0, a0
+
+
+def _shim_forwards(es, model, sc, forwards, arrays, prefix, n_layer):
+    """One reference shim run: reset, then every (ids, position_ids) of
+    `forwards` in turn on the same cache.  Stores per forward the logits and, per
+    layer, the write inputs and either the dequantized K/V (Python path) or the
+    attend query and output (kernel path) under ``{prefix}[_f{n}]_...``; returns
+    get_ecc_stats() after each forward and which layers took the kernel path."""
+    import torch
+    stats, fast = [], []
+    with torch.no_grad(), _record_shim(es) as rec, es.patch_model_with_ecc_attention(model, sc, num_blocks=16):
+        es.reset_ecc_cache(model)
+        for f, (ids, pos) in enumerate(forwards):
+            for lst in rec.values():
+                lst.clear()
+            out = model(ids) if pos is None else model(ids, position_ids=pos)
+            stats.append({k: int(v) for k, v in es.get_ecc_stats(model).items()})
+            p = prefix if len(forwards) == 1 else f"{prefix}_f{f}"
+            arrays[f"{p}_logits"] = out.logits.float().numpy()
+            assert [w[0] for w in rec["write"]] == list(range(n_layer))
+            assert sorted([x[0] for x in rec["kv"]] + [x[0] for x in rec["fast"]]) == list(range(n_layer))
+            for layer, k, v in rec["write"]:
+                arrays[f"{p}_l{layer}_k_in"] = k.numpy()
+                arrays[f"{p}_l{layer}_v_in"] = v.numpy()
+            for layer, kf, vf in rec["kv"]:
+                arrays[f"{p}_l{layer}_k_deq"] = kf.numpy()
+                arrays[f"{p}_l{layer}_v_deq"] = vf.numpy()
+            for layer, q, o in rec["fast"]:
+                arrays[f"{p}_l{layer}_q"] = q.numpy()
+                arrays[f"{p}_l{layer}_out"] = o.numpy()
+            fast.append(len(rec["fast"]) == n_layer)
+            assert fast[-1] or not rec["fast"]
+    return stats, fast
+
+
+LLAMA_CFG = dict(vocab_size=61, hidden_size=64, intermediate_size=128, num_hidden_layers=2,
+                 num_attention_heads=4, num_key_value_heads=2, max_position_embeddings=64,
+                 tie_word_embeddings=True)
+
+
+def _llama(kv_heads=2):
+    """The offline random-init fp32 LLaMA of the shim_llama* fixtures: 4 query
+    heads over `kv_heads` cache heads, head_dim 16 (Golay rows of 6 codewords
+    with 2 pad values), a 20-token prompt (1.25 blocks of 16) and 2 step tokens."""
+    import torch
+    from transformers import LlamaConfig, LlamaForCausalLM
+    torch.manual_seed(0)
+    cfg = dict(LLAMA_CFG, num_key_value_heads=kv_heads)
+    model = LlamaForCausalLM(LlamaConfig(**cfg)).eval()
+    ids = torch.randint(0, cfg["vocab_size"], (1, 20), generator=torch.Generator().manual_seed(3))
+    steps = torch.randint(0, cfg["vocab_size"], (1, 2), generator=torch.Generator().manual_seed(4))
+    return model, cfg, ids, steps
+
+
+def _weights(model, tag="w_"):
+    return {tag + k.replace(".", "__"): v.numpy() for k, v in model.state_dict().items()}
+
+
+def _same_weights(name, model):
+    """The model's weights are the w_* arrays of fixture `name`, which the tests load."""
+    with np.load(os.path.join(OUT, name + ".npz")) as z:
+        w = _weights(model)
+        assert sorted(w) == sorted(k for k in z.files if k.startswith("w_"))
+        assert all(np.array_equal(z[k], v) for k, v in w.items()), name
+
+
+def _step_forwards(ids, steps):
+    import torch
+    n = ids.shape[1]
+    return [(ids, None)] + [(steps[:, s:s + 1], torch.tensor([[n + s]])) for s in range(steps.shape[1])]
+
+
+def gen_shim_llama(manifest):
+    """The reference shim's prefill on a LLaMA-architecture model (RoPE, GQA: 4
+    query heads over 2 KV heads): every codec at BER 1e-2 (fp16 at 0), with the
+    post-RoPE K and the V that ECCBackend.write was given and the dequantized
+    K/V handed to _run_attention, per layer."""
+    import kv_cache.ecc_shim as es
+    model, cfg, ids, _ = _llama()
+    arrays = {"input_ids": ids.numpy(), **_weights(model)}
+    params = []
+    runs = [("hamming84", 1e-2, False), ("hamming84", 1e-2, True), ("golay", 1e-2, False),
+            ("hamming74", 1e-2, False), ("int4", 1e-2, False), ("fp16", 0.0, False)]
+    for i, (codec, ber, interp) in enumerate(runs):
+        for ber in ((ber, 2e-2) if codec == "hamming84" else (ber,)):
+            sc = es.ECCShimConfig(codec=codec, ber=ber, inject_errors=ber > 0, seed=42, block_size=16,
+                                  use_interpolation=interp)
+            t0 = time.time()
+            (st,), _ = _shim_forwards(es, model, sc, [(ids, None)], arrays, f"r{i}", cfg["num_hidden_layers"])
+            if codec != "hamming84" or st["errors_detected"] > 0:
+                break
+        assert codec != "hamming84" or st["errors_detected"] > 0  # doubles: interpolation has work
+        params.append({"codec": codec, "ber": ber, "use_interpolation": interp, "stats": st})
+        print(f"    shim llama {codec} ber={ber} interp={interp}: {st} ({time.time() - t0:.1f}s)")
+    _save("shim_llama", manifest, {"model": cfg, "runs": params, "seq_len": 20, "dtype": "float32"}, **arrays)
+
+
+def _gen_steps(name, manifest, es, models, runs, arrays, extra):
+    """Prefill + single-token forwards with explicit position_ids, per run; the
+    statistics of a run are a list, one get_ecc_stats() per forward."""
+    params = []
+    for i, (which, codec, ber, interp) in enumerate(runs):
+        model, cfg, ids, steps, n_layer = models[which]
+        sc = es.ECCShimConfig(codec=codec, ber=ber, inject_errors=True, seed=42, block_size=16,
+                              use_interpolation=interp)
+        t0 = time.time()
+        stats, fast = _shim_forwards(es, model, sc, _step_forwards(ids, steps), arrays, f"r{i}", n_layer)
+        # the kernel path is Hamming(8,4) without interpolation at seq_len == 1, and nothing else
+        assert fast == [False] + [codec == "hamming84" and not interp] * steps.shape[1]
+        assert not interp or stats[0]["errors_detected"] > 0
+        params.append({"model": which, "codec": codec, "ber": ber, "use_interpolation": interp,
+                       "fast_path": fast[-1], "stats": stats})
+        print(f"    {name} {which} {codec} interp={interp}: {stats[0]} -> {stats[-1]} ({time.time() - t0:.1f}s)")
+    _save(name, manifest, dict(extra, runs=params), **arrays)
+
+
+def gen_shim_gpt2_steps(manifest):
+    """The reference shim in its default mode over a prefill and four single-token
+    forwards of the gen_shim GPT-2: every forward writes from position 0 (the step's
+    token lands in slot 0, context_len stays 20), _injection_count runs on, and
+    the Hamming(8,4) steps without interpolation take paged_attention_ecc, which
+    counts nothing.  The model is gen_shim's (same config and seed): its weights
+    are in shim_gpt2.npz and not repeated here."""
+    import torch
+    from transformers import GPT2Config, GPT2LMHeadModel
+    import kv_cache.ecc_shim as es
+    torch.manual_seed(0)
+    cfg = dict(n_layer=2, n_head=4, n_embd=64, n_positions=64, vocab_size=97)
+    model = GPT2LMHeadModel(GPT2Config(**cfg)).eval()
+    _same_weights("shim_gpt2", model)
+    ids = torch.randint(0, 97, (1, 20), generator=torch.Generator().manual_seed(3))
+    steps = torch.randint(0, 97, (1, 4), generator=torch.Generator().manual_seed(4))
+    arrays = {"input_ids": ids.numpy(), "step_ids": steps.numpy()}
+    runs = [("gpt2", "hamming84", 1e-2, False), ("gpt2", "hamming84", 1e-2, True), ("gpt2", "golay", 1e-2, False)]
+    _gen_steps("shim_gpt2_steps", manifest, es, {"gpt2": (model, cfg, ids, steps, 2)}, runs, arrays,
+               {"model": cfg, "weights": "shim_gpt2", "seq_len": 20, "steps": 4, "dtype": "float32"})
+
+
+def gen_shim_llama_steps(manifest):
+    """The same on the shim_llama model (its weights are in shim_llama.npz, not
+    repeated here) over a prefill and two steps: Golay (Python path, GQA),
+    Hamming(8,4) on the kernel path with GQA -- where the reference kernel reads
+    cache head h with the caches strided by H, not h // groups -- and on an MHA
+    twin (4 KV heads, same seed; weights stored here as m_w_*)."""
+    import kv_cache.ecc_shim as es
+    gqa, mha = _llama(2), _llama(4)
+    _same_weights("shim_llama", gqa[0])
+    ids, steps = gqa[2], gqa[3]
+    arrays = {"input_ids": ids.numpy(), "step_ids": steps.numpy(), **_weights(mha[0], "m_w_")}
+    runs = [("gqa", "golay", 1e-2, False), ("gqa", "hamming84", 1e-2, False), ("mha", "hamming84", 1e-2, False)]
+    _gen_steps("shim_llama_steps", manifest, es, {"gqa": gqa + (2,), "mha": mha + (2,)}, runs, arrays,
+               {"models": {"gqa": gqa[1], "mha": mha[1]}, "gqa_weights": "shim_llama", "seq_len": 20,
+                "steps": 2, "dtype": "float32"})
+
+
 def gen_attention(manifest):
     """Pin paged_attention_ecc (kv_cache/attention_ecc.py:620-780).
 
@@ -430,7 +617,8 @@ def gen_attention(manifest):
 
 GENERATORS = {"hamming": gen_hamming, "golay": gen_golay, "inject": gen_inject,
               "interp": gen_interp, "fused": gen_fused, "shim": gen_shim, "shim_fp16": gen_shim_fp16,
-              "attention": gen_attention}
+              "attention": gen_attention, "shim_llama": gen_shim_llama,
+              "shim_gpt2_steps": gen_shim_gpt2_steps, "shim_llama_steps": gen_shim_llama_steps}
 
 
 def main():
@@ -443,17 +631,21 @@ def main():
     sys.path.insert(0, args.ref)
     os.makedirs(OUT, exist_ok=True)
     mpath = os.path.join(OUT, "MANIFEST.json")
-    manifest = {}
-    if os.path.exists(mpath):
-        with open(mpath) as f:
-            manifest = json.load(f)
+    new = {}
     for name, fn in GENERATORS.items():
         if args.only and name not in args.only:
             continue
         print(f"[{name}]")
         t0 = time.time()
-        fn(manifest)
+        fn(new)
         print(f"  done in {time.time() - t0:.1f}s")
+    # entries of fixtures not regenerated stay as they are (read now, not at the
+    # start: a slow --only run does not drop what another one added meanwhile)
+    manifest = {}
+    if os.path.exists(mpath):
+        with open(mpath) as f:
+            manifest = json.load(f)
+    manifest.update(new)
     manifest["_generator"] = {"script": "tools/gen_golden.py", "mode": "TRITON_INTERPRET=1",
                               "reference_snapshot": "2026-01-28"}
     with open(mpath, "w") as f:
