@@ -411,7 +411,8 @@ KVECC_API int kvecc_shim_read_batch(const void *k_cache, const void *v_cache, co
 /* ---- Paged decode attention with inline ECC decode ---------------------------- */
 /* attention_ecc.py:620-780 (paged_attention_ecc) + :265-427 (kernel): one query
  * token per sequence, query [batch, heads, head_dim] (q_dtype), caches as above
- * (codec H84: uint8, double errors keep their data; GOLAY: int32, uncorrectable
+ * (codec H84: uint8, double errors keep their data -- kvecc_paged_attention_interp
+ * below interpolates them; GOLAY: int32, uncorrectable
  * data kept; GOLAY_PACKED: 3-byte codewords, rows of KVECC_GOLAY_PACKED_ROW bytes), block_table [batch, max_blocks] int32 (-1 = no block, token
  * skipped), context_lens [batch] int32, max_context_len (<= 0 means
  * max_blocks*block_size; a context_len above it, or above the table's
@@ -485,6 +486,46 @@ KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_ba
                                                  int64_t layer, int64_t block_size, int64_t max_blocks,
                                                  int64_t max_context_len, float sm_scale, int codec,
                                                  float *workspace, int64_t workspace_floats, void *stream);
+
+/* Interpolated attention (Hamming(8,4) with temporal interpolation of detected
+ * double errors: the reference's config 4, interpolation_triton.py).  The
+ * arguments, the workspace (kvecc_paged_attention_chunk_workspace at q_len =
+ * q_max), the query strides, the output layout [batch, q_max, heads, head_dim],
+ * the empty value -8.0, the GQA map and every other rule are
+ * kvecc_paged_attention_chunk_ragged's, except that q_spans may be NULL (the
+ * uniform call: first 0, count q_max) and q_max 1 is allowed and is the decode
+ * step.  codec must be KVECC_CODEC_H84, and the caches must be under 4 GiB;
+ * anything else is KVECC_EINVAL with a message (callers fall back).  No
+ * statistics are kept.
+ *
+ * Interpolation is a property of the stored key / value, not of the query row
+ * that looks at it.  With n_b = min(context_lens[b], max_context_len,
+ * max_blocks*block_size), the value used for position l < n_b of sequence b is
+ * bit for bit what kvecc_shim_read(..., ctx = n_b, interp = 1) gives for that
+ * sequence alone: every byte decodes with the SECDED decoder; a byte of type 2
+ * (double detected) becomes min(15, (L + R + 1) >> 1), where L and R are the
+ * decoded, NOT interpolated, values of the same (head, d) element at positions
+ * max(l - 1, 0) and min(l + 1, n_b - 1); a neighbour whose block-table entry is
+ * < 0 reads as 0; a row whose own block is < 0 is skipped, as everywhere.
+ * Consequences: in a chunk call the last key a query row sees, p_t, is
+ * interpolated from key p_t + 1 when p_t + 1 < n_b although the row does not
+ * attend to that key -- the neighbour bound is the sequence's length, never the
+ * row's, the column's or the tile's key limit -- so row t is NOT the decode
+ * call at context_lens = p_t + 1 whenever key p_t holds a double.  A batched
+ * rectangular kvecc_shim_read_batch interpolates a shorter sequence's last
+ * token against the zero row past its length; this entry clamps per sequence,
+ * as the reference kernel does.  Launch geometry comes from batch, q_max and
+ * heads only: all-full spans return the uniform call's bits. */
+KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                           int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                           const void *v_cache, const int32_t *block_table,
+                                           const int32_t *context_lens, const int32_t *q_spans,
+                                           const float *k_scales, const float *v_scales, void *out,
+                                           int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                           int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                           int64_t layer, int64_t block_size, int64_t max_blocks,
+                                           int64_t max_context_len, float sm_scale, int codec,
+                                           float *workspace, int64_t workspace_floats, void *stream);
 
 /* ---- Cache scrub --------------------------------------------------------------- */
 /* In-place patrol scrub of a resident paged cache (no reference counterpart:
@@ -661,6 +702,18 @@ KVECC_API int kvecc_cpu_paged_attention_chunk_ragged(const void *query, int64_t 
                                                      int64_t layer, int64_t block_size, int64_t max_blocks,
                                                      int64_t max_context_len, float sm_scale, int codec,
                                                      int threads);
+/* host twin of kvecc_paged_attention_interp (q_spans may be NULL) */
+KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batch_stride,
+                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                               const void *k_cache, const void *v_cache,
+                                               const int32_t *block_table, const int32_t *context_lens,
+                                               const int32_t *q_spans, const float *k_scales,
+                                               const float *v_scales, void *out, int64_t batch,
+                                               int64_t q_max, int64_t heads, int64_t kv_heads,
+                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                               int64_t layer, int64_t block_size, int64_t max_blocks,
+                                               int64_t max_context_len, float sm_scale, int codec,
+                                               int threads);
 
 #ifdef __cplusplus
 }

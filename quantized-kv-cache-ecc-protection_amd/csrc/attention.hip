@@ -2,7 +2,9 @@
 // the codewords inline: kvecc_paged_attention (one query token per sequence,
 // the decode step) and kvecc_paged_attention_chunk (q_len tokens per sequence,
 // causal: a prefill, a chunk, a verify step's draft tokens; no reference
-// counterpart).  The chunked entry runs the same kernel bodies (attn_*_body.inc)
+// counterpart), and kvecc_paged_attention_interp (the chunk form over a
+// Hamming(8,4) cache with detected double errors interpolated from the
+// neighbouring tokens, in kernels of its own).  The chunked entry runs the same kernel bodies (attn_*_body.inc)
 // under kernel names of its own: the matrix-core kernels with 16 (token, head)
 // columns per workgroup and a per-column key limit (ChunkMap), the split
 // kernels over a virtual batch of batch * q_len rows (ChunkArgs).
@@ -159,6 +161,34 @@ struct ChunkSpan {
 };
 template <typename A>
 constexpr bool is_chunk = std::is_base_of<ChunkArgs, A>::value;
+
+// Interpolating calls (kvecc_paged_attention_interp, Hamming(8,4) only) run
+// kernels of their own names over an argument block of their own type: every
+// other kernel keeps its text, its arguments and its registers.  The block
+// adds nothing to RaggedArgs yet -- the neighbour rule needs only the sequence's
+// length, which context_lens and ctx_cap give.
+struct InterpArgs : RaggedArgs {};
+template <typename A>
+constexpr bool is_interp = std::is_same<A, InterpArgs>::value;
+
+// The first look of the interpolating kernels: bit 3 of each byte that is a
+// type-2 codeword (double detected: syndrome != 0, overall parity even) -- the
+// scrubber's h84_dirty4 and four more operations.
+__device__ __forceinline__ uint32_t h84_double4(uint32_t w) {
+  const uint32_t c = h_code4(w);  // syndrome in bits 0..2, parity error in bit 4 of each byte
+  return ((c & 0x07070707u) + 0x07070707u) & ~(c >> 1) & 0x08080808u;
+}
+// ... and their slow path: four codewords decoded, the doubles replaced by
+// interp_word of the neighbours' decoded (not interpolated) values wl / wr, and
+// re-encoded, so that the corrected nibbles take the operand path of every
+// other byte (the decode table); bytes that are no double keep their data
+__device__ __forceinline__ uint32_t h84_interp_fix4(uint32_t w, uint32_t wl, uint32_t wr) {
+  uint32_t q, ty, ql, qr, tt, n1 = 0, n2 = 0;
+  h84_decode4(w, q, ty, n1, n2);
+  h84_decode4(wl, ql, tt, n1, n2);
+  h84_decode4(wr, qr, tt, n1, n2);
+  return h84_encode4(interp_word(q, ql, qr, ty));
+}
 
 // Lane chunk c of a token row: VEC 32-bit words = 4*VEC H(8,4) codewords, or
 // VEC Golay codewords (3*VEC values; codewords past the row's last are read
@@ -544,6 +574,16 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_chunk_kernel(RaggedAr
 #include "attn_split_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the general path of an interpolating call (kvecc_paged_attention_interp): the chunk form
+// with the [interpolation] island, Hamming(8,4) over buffer-addressed caches only
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_interp_kernel(InterpArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 2
+#include "attn_split_body.inc"
+#undef ATTN_BODY_CHUNK
+}
 
 // ---- GQA on the matrix cores (Hamming(8,4), fp16 queries) -----------------------
 //
@@ -723,6 +763,14 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_ragged_kernel(R
 #include "attn_h84_mfma_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the interpolating entry's: the ragged form with double errors interpolated
+// from the neighbouring tokens before the operands are built (a body of its own)
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_interp_kernel(InterpArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#include "attn_h84_mfma_interp_body.inc"
+}
 
 // ---- GQA on the matrix cores, Golay(24,12) int32 caches, head_dim 128 ---------
 //
@@ -785,7 +833,10 @@ static int pow2_at_least(int64_t x) {
 // chunked call's over its virtual batch (ChunkArgs)
 #define KVECC_SPLIT_LAUNCH(VEC_, WW, BUF_, G_)                                                                  \
   do {                                                                                                          \
-    if constexpr (is_chunk<A>)                                                                                  \
+    if constexpr (is_interp<A>) {                                                                               \
+      if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                           \
+        KVECC_LAUNCH((paged_attn_split_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
+    } else if constexpr (is_chunk<A>)                                                                           \
       KVECC_LAUNCH((paged_attn_split_chunk_kernel<T, CODEC, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
     else                                                                                                        \
       KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
@@ -1019,6 +1070,32 @@ static int launch_mfma_chunk(int codec, const RaggedArgs &a, int64_t batch, int6
   return KVECC_OK;
 }
 
+// the interpolating entry's matrix-core kernels (uniform calls too: the spans are nullable)
+static int launch_mfma_interp(const InterpArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
+  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
+  switch (a.d) {
+    case 32: KVECC_LAUNCH((paged_attn_h84_mfma_interp_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
+    case 64: KVECC_LAUNCH((paged_attn_h84_mfma_interp_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
+    default: KVECC_LAUNCH((paged_attn_h84_mfma_interp_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
+  }
+  launch_combine<__half>(a, batch * a.q_len, st);
+  return KVECC_OK;
+}
+// ... and its general path: launch_codec_rows for the interpolating split kernels
+template <typename T>
+static int launch_interp_rows(InterpArgs a, int64_t rows, int gq, hipStream_t st) {
+  const int64_t wg_per_row = a.heads / gq;
+  if (rows * wg_per_row <= kMaxGridY) return launch_attn<T, KVECC_CODEC_H84>(a, rows, gq, st);
+  const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
+  for (int64_t vb = 0; vb < rows; vb += per) {
+    a.vb0 = (uint32_t)vb;
+    const int rc = launch_attn<T, KVECC_CODEC_H84>(a, std::min(per, rows - vb), gq, st, false);
+    if (rc != KVECC_OK) return rc;
+  }
+  launch_combine<T>(a, rows, st);
+  return KVECC_OK;
+}
+
 // tokens per workgroup: the largest power of two <= kMaxSplit that still gives
 // >= per_cu workgroups per CU (small batch*heads decode steps split finer); 8
 // per CU made every codec 1-15 % slower
@@ -1186,6 +1263,8 @@ KVECC_API int64_t kvecc_paged_attention_chunk_workspace(int64_t batch, int64_t q
 
 // q_spans: null for kvecc_paged_attention_chunk, the device spans for the ragged entry (q_len its q_max).
 // Nothing but the kernels reads the spans: the launch geometry is the uniform call's.
+// interp: kvecc_paged_attention_interp -- Hamming(8,4) caches under 4 GiB through the interpolating
+// kernels at every q_len (q_len 1 included: the decode entry's kernels do not interpolate).
 static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
                                       int64_t q_head_stride, int q_dtype, const void *k_cache,
                                       const void *v_cache, const int32_t *block_table,
@@ -1195,9 +1274,11 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
                                       int64_t num_blocks, int64_t num_layers, int64_t layer,
                                       int64_t block_size, int64_t max_blocks, int64_t max_context_len,
                                       float sm_scale, int codec, float *workspace, int64_t workspace_floats,
-                                      void *stream) {
+                                      void *stream, bool interp = false) {
   if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
+  if (interp && codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
   if (batch == 0 || q_len == 0 || heads == 0) return KVECC_OK;
   if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
       (heads > 1 && q_head_stride < head_dim) || (q_len > 1 && q_token_stride < head_dim))
@@ -1206,7 +1287,7 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
                      (long long)head_dim);
   // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
   // (a ragged call stays here: the decode entry knows no spans)
-  if (!q_spans && q_len == 1 && (heads == 1 || q_head_stride == head_dim) &&
+  if (!interp && !q_spans && q_len == 1 && (heads == 1 || q_head_stride == head_dim) &&
       (batch == 1 || q_batch_stride == heads * head_dim))
     return kvecc_paged_attention(query, q_dtype, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, batch, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size,
@@ -1239,7 +1320,7 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   if (workspace_floats < need)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: workspace %lld < %lld floats",
                      (long long)workspace_floats, (long long)need);
-  RaggedArgs a;
+  InterpArgs a;  // RaggedArgs for every other entry's kernels
   a.q = query;
   a.k_cache = k_cache;
   a.v_cache = v_cache;
@@ -1276,9 +1357,12 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   const bool fits = cb <= 0xFFFFFFFFLL && rows_total * 4 <= 0xFFFFFFFFLL;
   a.cache_bytes = fits ? (uint32_t)cb : 0u;  // 0 selects the 64-bit-addressed kernels
   a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
+  if (interp && !fits)
+    return set_error(KVECC_EINVAL, "paged_attention_interp: caches of 4 GiB or more are not supported");
   const int gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
-  // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound)
-  int gm = q_len > 1 ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
+  // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound);
+  // an interpolating call takes its matrix-core kernels at q_len 1 too (one tile, the same bound: `finest`)
+  int gm = q_len > 1 || interp ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
                                              head_dim, heads, kv_heads, fits)
                      : 0;
   int64_t wgs = 0;  // workgroups per split
@@ -1324,7 +1408,15 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   }
   hipStream_t st = as_stream(stream);
   int rc;
-  if (gm) {
+  if (interp && gm) {
+    rc = launch_mfma_interp(a, batch, tiles, st);
+  } else if (interp) {
+    switch (q_dtype) {
+      case KVECC_F32: rc = launch_interp_rows<float>(a, vbatch, gq, st); break;
+      case KVECC_F16: rc = launch_interp_rows<__half>(a, vbatch, gq, st); break;
+      default: rc = launch_interp_rows<__hip_bfloat16>(a, vbatch, gq, st); break;
+    }
+  } else if (gm) {
     rc = launch_mfma_chunk(codec, a, batch, tiles, st);
   } else {
     switch (q_dtype) {
@@ -1371,6 +1463,22 @@ KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_ba
                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
+}
+
+KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                           int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                           const void *v_cache, const int32_t *block_table,
+                                           const int32_t *context_lens, const int32_t *q_spans,
+                                           const float *k_scales, const float *v_scales, void *out,
+                                           int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                           int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                           int64_t layer, int64_t block_size, int64_t max_blocks,
+                                           int64_t max_context_len, float sm_scale, int codec,
+                                           float *workspace, int64_t workspace_floats, void *stream) {
+  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream, true);
 }
 
 }  // extern "C"

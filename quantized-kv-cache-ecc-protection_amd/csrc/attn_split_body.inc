@@ -3,6 +3,8 @@
 // nullable query spans), included
 // by attention.hip inside each kernel: the decode kernel's text is what it
 // always was, so its code is too (see ChunkArgs).
+// paged_attn_split_interp_kernel includes it at ATTN_BODY_CHUNK 2 (`a` an InterpArgs): the chunk
+// form plus the [interpolation] island; at 0 and 1 the preprocessed text is what it was.
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
   constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
   using C = Chunk<CODEC, VEC>;
@@ -215,6 +217,45 @@
       ok[u] = pok[u];
     }
     if (kPrefetch && i0 + TP * U < ntok) load_rows(i0 + TP * U);
+#if ATTN_BODY_CHUNK == 2  // [interpolation] paged_attn_split_interp_kernel only (kvecc.h "Interpolated attention")
+    // First look: h84_double4 of the lane's words.  A lane whose K or V words of
+    // a row hold a type-2 byte re-loads the same words of the rows at positions
+    // max(l - 1, 0) and min(l + 1, n_b - 1) of its sequence -- through the block
+    // table, a -1 block reading as zero codewords -- and replaces its words by
+    // the interpolated, re-encoded ones (h84_interp_fix4).
+    if (live) {
+      const int64_t nb = min<int64_t>(a.ctx_lens[bt], a.ctx_cap);  // the sequence's length: the neighbours' clamp
+      const int32_t head_row0 = (int32_t)((a.layer * a.kv_heads + hk) * a.bs);
+      const int32_t blk_rows = (int32_t)(a.layers * a.kv_heads * a.bs);
+      auto row_at = [&](int64_t p) {
+        const uint32_t lb = (uint32_t)p / (uint32_t)a.bs;
+        const int32_t blk = a.table[(int64_t)bt * a.max_blocks + lb];
+        return blk < 0 ? -1 : blk * blk_rows + head_row0 + (int32_t)((uint32_t)p - lb * (uint32_t)a.bs);
+      };
+      auto word_at = [&](__amdgpu_buffer_rsrc_t rs, int32_t row, int k) {
+        if (row < 0) return 0u;
+        return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
+            rs, (uint32_t)row * (uint32_t)a.d + 4u * VEC * cs + 4u * k, 0, 0);
+      };
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        uint32_t dbl = 0;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) dbl |= h84_double4(kc[u].w[k]) | h84_double4(vc[u].w[k]);
+        if (dbl && ok[u]) {
+          const int64_t pos = t0 + i0 + u * TP;  // < ntok + t0 <= n_b: ok[u]
+          const int32_t rl = row_at(max<int64_t>(pos - 1, 0)), rr = row_at(min<int64_t>(pos + 1, nb - 1));
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            if (h84_double4(kc[u].w[k]))
+              kc[u].w[k] = h84_interp_fix4(kc[u].w[k], word_at(krs, rl, k), word_at(krs, rr, k));
+            if (h84_double4(vc[u].w[k]))
+              vc[u].w[k] = h84_interp_fix4(vc[u].w[k], word_at(vrs, rl, k), word_at(vrs, rr, k));
+          }
+        }
+      }
+    }
+#endif
     float sc[G][U];
     float mn[G];
 #pragma unroll

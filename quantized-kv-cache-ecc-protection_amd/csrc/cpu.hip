@@ -1017,9 +1017,12 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
                               void *out, int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
                               int64_t head_dim, int64_t num_blocks, int64_t num_layers, int64_t layer,
                               int64_t block_size, int64_t max_blocks, int64_t max_context_len,
-                              float sm_scale, int codec, int threads, const int32_t *q_spans = nullptr) {
+                              float sm_scale, int codec, int threads, const int32_t *q_spans = nullptr,
+                              bool interp = false) {
   if (batch < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: negative size");
+  if (interp && codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
   if (batch == 0 || heads == 0 || q_len == 0) return KVECC_OK;
   if (kv_heads < 1 || heads % kv_heads != 0)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: heads not a multiple of kv heads");
@@ -1046,7 +1049,10 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
   const int64_t groups = heads / kv_heads;
   parallel_for(batch * q_len * heads, threads, 1, [&](int64_t b0, int64_t e0, int) {
     std::vector<float> q(head_dim), kv(head_dim), acc(head_dim);
-    auto decode_row = [&](const void *cache, int64_t srow, float s) {
+    const std::vector<uint8_t> zero_row(golay ? 0 : (size_t)head_dim, 0);  // a missing block's codewords
+    // cl / cr (interpolating calls): the codewords of the row's neighbours
+    auto decode_row = [&](const void *cache, int64_t srow, float s, const uint8_t *cl = nullptr,
+                          const uint8_t *cr = nullptr) {
       if (golay) {
         for (int64_t k = 0; k < g; ++k) {
           uint32_t cnt, w;
@@ -1065,6 +1071,12 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
         for (int64_t j = 0; j < head_dim; ++j) {
           uint32_t d, t, n1 = 0, n2 = 0;
           h84_decode4(c[j], d, t, n1, n2);
+          if (cl) {  // a double becomes the rounded mean of its neighbours' decoded values
+            uint32_t dl, dr, tt;
+            h84_decode4(cl[j], dl, tt, n1, n2);
+            h84_decode4(cr[j], dr, tt, n1, n2);
+            d = interp_word(d, dl, dr, t) & 0xFFu;
+          }
           kv[j] = ((float)d - 8.0f) * s;
         }
       }
@@ -1082,19 +1094,37 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
           valid ? std::min<int64_t>(std::min<int64_t>((int64_t)context_lens[b] - count + 1 + (t - first), max_context_len),
                                     max_blocks * block_size)
                 : 0;
+      // the sequence's length, which the neighbours of an interpolating call clamp to (not the row's key limit)
+      const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
+      auto slot_of = [&](int64_t pos) {  // -1: no block
+        const int32_t blk = block_table[b * max_blocks + pos / block_size];
+        return blk < 0 ? (int64_t)-1
+                       : (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
+      };
+      auto codewords = [&](const void *cache, int64_t slot) {
+        return slot < 0 ? zero_row.data() : reinterpret_cast<const uint8_t *>(cache) + slot * head_dim;
+      };
       for (int64_t pos = 0; pos < ctx; ++pos) {
         const int32_t blk = block_table[b * max_blocks + pos / block_size];
         if (blk < 0) continue;
         const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size +
                              pos % block_size;
-        decode_row(k_cache, srow, k_scales[srow]);
+        const int64_t sl = interp ? slot_of(pos > 0 ? pos - 1 : 0) : -1;
+        const int64_t sr = interp ? slot_of(pos + 1 < nb ? pos + 1 : nb - 1) : -1;
+        if (interp)
+          decode_row(k_cache, srow, k_scales[srow], codewords(k_cache, sl), codewords(k_cache, sr));
+        else
+          decode_row(k_cache, srow, k_scales[srow]);
         float sc = 0.0f;
         for (int64_t j = 0; j < head_dim; ++j) sc += q[j] * kv[j];
         sc *= sm_scale;
         const float mn = std::max(m, sc);
         const float alpha = m == -INFINITY ? 0.0f : std::exp(m - mn);
         const float beta = std::exp(sc - mn);
-        decode_row(v_cache, srow, v_scales[srow]);
+        if (interp)
+          decode_row(v_cache, srow, v_scales[srow], codewords(v_cache, sl), codewords(v_cache, sr));
+        else
+          decode_row(v_cache, srow, v_scales[srow]);
         for (int64_t j = 0; j < head_dim; ++j) acc[j] = alpha * acc[j] + beta * kv[j];
         l = alpha * l + beta;
         m = mn;
@@ -1162,6 +1192,32 @@ KVECC_API int kvecc_cpu_paged_attention_chunk_ragged(const void *query, int64_t 
                             block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads, kv_heads,
                             head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
                             sm_scale, codec, threads, q_spans);
+}
+
+// Interpolating twin (kvecc_paged_attention_interp): every stored byte through h84_decode4,
+// doubles through interp_word of the neighbouring tokens (clamped to the sequence), then the
+// attention above; q_spans may be null
+KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batch_stride,
+                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                               const void *k_cache, const void *v_cache,
+                                               const int32_t *block_table, const int32_t *context_lens,
+                                               const int32_t *q_spans, const float *k_scales,
+                                               const float *v_scales, void *out, int64_t batch,
+                                               int64_t q_max, int64_t heads, int64_t kv_heads,
+                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                               int64_t layer, int64_t block_size, int64_t max_blocks,
+                                               int64_t max_context_len, float sm_scale, int codec,
+                                               int threads) {
+  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: negative q_max");
+  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
+      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: bad query strides");
+  if (head_dim % 4 != 0)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: hamming84 head_dim must be a multiple of 4");
+  return cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                            block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads, kv_heads,
+                            head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
+                            sm_scale, codec, threads, q_spans, true);
 }
 
 }  // extern "C"

@@ -76,6 +76,9 @@ SIGNATURES = {
     "kvecc_paged_attention_chunk_ragged": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                            _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
                                            _vp, _i64, _vp],
+    "kvecc_paged_attention_interp": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                     _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
+                                     _vp, _i64, _vp],
     "kvecc_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                           _int, _vp, _vp],
     "kvecc_cpu_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -117,6 +120,9 @@ SIGNATURES = {
     "kvecc_cpu_paged_attention_chunk_ragged": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                                _f32, _int, _int],
+    "kvecc_cpu_paged_attention_interp": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                         _f32, _int, _int],
 }
 _RESTYPE = {
     "kvecc_version": ctypes.c_char_p,

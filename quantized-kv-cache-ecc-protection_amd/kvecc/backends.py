@@ -28,8 +28,10 @@ FUNCTIONS = (
 
 # Native extensions beyond the reference's set that the two built-in backends
 # ("hip", "cpu") both provide; a registered third-party backend may lack them
-# (the shim then raises where it needs one): the in-place cache scrub.
-NATIVE_FUNCTIONS = ("cache_scrub_tensors",)
+# (the shim then raises where it needs one): the in-place cache scrub, and the
+# paged attention entries (paged_attention_chunk_into takes interp=True: the
+# interpolating attention of ECCShimConfig(interp_attention=True)).
+NATIVE_FUNCTIONS = ("cache_scrub_tensors", "paged_attention_into", "paged_attention_chunk_into")
 
 # backend name -> module implementing FUNCTIONS
 CODEC_BACKENDS = {

@@ -617,7 +617,12 @@ def shim_read_batch(k_cache, v_cache, k_scales, v_scales, block_table, ctx, head
 # ============================================================================
 
 def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                         out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
+                         out, layer_idx, block_size, sm_scale, codec, max_context_len=0, interp=False):
+    if interp:  # the one-token call of kvecc_cpu_paged_attention_interp
+        paged_attention_chunk_into(query.unsqueeze(1), k_cache, v_cache, block_table, context_lens, k_scales,
+                                   v_scales, out.unsqueeze(1), layer_idx, block_size, sm_scale, codec,
+                                   max_context_len=max_context_len, interp=True)
+        return out
     batch, heads, head_dim = query.shape
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
@@ -630,15 +635,27 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
 
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None):
+                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
+                               interp=False):
     """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
-    from .ops import _check_attention_chunk_args, _check_q_spans
+    from .ops import _check_attention_chunk_args, _check_interp_codec, _check_q_spans
     _check_cpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
+    if interp:
+        _check_interp_codec(codec)
     batch, q_len, heads, head_dim = query.shape
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
+    if interp:
+        if q_spans is not None:
+            _check_q_spans(q_spans, batch, query.device)
+        _lib.call("kvecc_cpu_paged_attention_interp", _ptr(query), query.stride(0), query.stride(1),
+                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+                  int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
+        return out
     if q_spans is not None:
         _check_q_spans(q_spans, batch, query.device)
         _lib.call("kvecc_cpu_paged_attention_chunk_ragged", _ptr(query), query.stride(0), query.stride(1),

@@ -117,6 +117,14 @@ class ECCShimConfig:
     MHA and 4 query heads per cache head: profiles/chunk_attention/); fp32 and
     bf16 models and other head_dims run the split kernels once per query row,
     which re-decode the cache for each and have not been measured.
+    ``interp_attention`` (append mode, hamming84 with use_interpolation,
+    opt-in) sends every forward -- single-token steps, the prefill, chunks,
+    ragged spans -- through the interpolating paged attention
+    (kvecc_paged_attention_interp) when decode_stats is off and head_dim <= 256:
+    detected double errors are interpolated inside the kernel, no dense K / V
+    is read.  It keeps no statistics either.  Each sequence's last token clamps
+    at its own length, where the batched read interpolates a shorter sequence's
+    last token against the zero row past it.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -127,7 +135,7 @@ class ECCShimConfig:
     def __init__(self, codec="hamming84", ber=0.0, block_size=16, num_blocks=256,
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
-                 decode_stats=False, chunk_attention=False):
+                 decode_stats=False, chunk_attention=False, interp_attention=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -156,6 +164,10 @@ class ECCShimConfig:
         if chunk_attention and cache_mode != "append":
             raise ValueError("chunk_attention=True needs cache_mode='append'")
         self.chunk_attention = bool(chunk_attention)
+        if interp_attention and (cache_mode != "append" or codec != "hamming84" or not use_interpolation):
+            raise ValueError("interp_attention=True needs cache_mode='append', codec='hamming84' and "
+                             "use_interpolation=True")
+        self.interp_attention = bool(interp_attention)
 
 
 class SimpleBlockManager:
@@ -654,6 +666,21 @@ class ECCBackend:
         if self._spans is not None:
             self._check_spans(b, q_len)
             spans = self._span_buf[:b]
+        if interp and cfg.interp_attention and not cfg.decode_stats and d <= 256:
+            # every q_len on the interpolating kernel: q read in place as [batch,
+            # q_len, heads, d], doubles interpolated inline, no dense K / V, no statistics
+            qt = q.transpose(1, 2)
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention_interp(
+                    qt, mgr.k_cache, mgr.v_cache, table, dev_lens, spans, mgr.k_scales, mgr.v_scales,
+                    layer_idx, mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, ctx)
+                return out.transpose(1, 2)
+            out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+            self.codec_backend.paged_attention_chunk_into(
+                qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx, q_spans=spans,
+                interp=True)
+            return out.transpose(1, 2)
         if q_len > 1 and cfg.chunk_attention and cfg.codec in ("hamming84", "golay") and not interp \
                 and not cfg.decode_stats and d <= 256:
             # prefill / chunk / verify step on the chunked causal kernel: q read

@@ -1168,8 +1168,11 @@ def _check_attention_rest(batch, heads, head_dim, device, k_cache, v_cache, bloc
 
 
 def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                         out, layer_idx, block_size, sm_scale, codec, max_context_len=0):
+                         out, layer_idx, block_size, sm_scale, codec, max_context_len=0, interp=False):
     """kvecc_paged_attention on [B, H, D] query / out (see include/kvecc.h).
+
+    interp=True (hamming84 only): double errors are interpolated from the
+    neighbouring tokens -- the one-token call of kvecc_paged_attention_interp.
 
     Every argument is validated (dtypes, geometry against codec and block_size,
     contiguity, one device): a mismatch raises ValueError instead of reading
@@ -1181,6 +1184,11 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
                           out, block_size, codec)
     if out.dtype != query.dtype:
         raise ValueError(f"out dtype {out.dtype} != query dtype {query.dtype}")
+    if interp:
+        paged_attention_chunk_into(query.unsqueeze(1), k_cache, v_cache, block_table, context_lens, k_scales,
+                                   v_scales, out.unsqueeze(1), layer_idx, block_size, sm_scale, codec,
+                                   max_context_len=max_context_len, interp=True)
+        return out
     batch, heads, head_dim = query.shape
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
@@ -1216,8 +1224,14 @@ def _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_le
         raise ValueError("out must be contiguous")
 
 
+def _check_interp_codec(codec):
+    if codec != "hamming84":
+        raise ValueError(f"interp needs hamming84, got codec {codec!r}")
+
+
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None):
+                               out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
+                               interp=False):
     """kvecc_paged_attention_chunk: q_len query tokens per sequence, causal (include/kvecc.h).
 
     query [B, q_len, H, D] with any strides and a unit innermost one (the
@@ -1230,10 +1244,17 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     q_spans (int32 [B, 3] on the device, see query_spans) makes the call ragged
     (kvecc_paged_attention_chunk_ragged): q_len is the rectangle's q_max,
     context_lens counts each sequence's own valid tokens, padding rows come out
-    as the empty value and their query elements are never read."""
+    as the empty value and their query elements are never read.
+
+    interp=True (hamming84 only; kvecc_paged_attention_interp): detected double
+    errors of the stored keys and values are interpolated from the neighbouring
+    tokens of their own sequence, as shim_read(interp=True) reads them; with or
+    without q_spans, q_len 1 included."""
     _check_gpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
+    if interp:
+        _check_interp_codec(codec)
     batch, q_len, heads, head_dim = query.shape
     if q_spans is not None:
         _check_q_spans(q_spans, batch, query.device)
@@ -1242,6 +1263,13 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
     ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
     ws = _attn_workspace(query.device, ws_n)
+    if interp:
+        _lib.call("kvecc_paged_attention_interp", _ptr(query), query.stride(0), query.stride(1),
+                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+                  mcl, float(sm_scale), SHIM_CODECS[codec], _ptr(ws), ws.numel(), _stream(query.device))
+        return out
     if q_spans is not None:
         _lib.call("kvecc_paged_attention_chunk_ragged", _ptr(query), query.stride(0), query.stride(1),
                   query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
@@ -1259,9 +1287,10 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
 
 def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                           layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0,
-                          q_spans=None):
+                          q_spans=None, interp=False):
     """paged_attention_chunk_into with a fresh [B, q_len, H, D] output; on the
-    GPU or, for host tensors, through the host twin.  q_spans: a ragged call."""
+    GPU or, for host tensors, through the host twin.  q_spans: a ragged call;
+    interp: double errors interpolated (hamming84)."""
     if sm_scale is None:
         sm_scale = 1.0 / math.sqrt(query.shape[-1])
     out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
@@ -1269,10 +1298,11 @@ def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_
         from . import cpu_ops
         return cpu_ops.paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
                                                   v_scales, out, layer_idx, block_size, sm_scale, codec,
-                                                  max_context_len=max_context_len, q_spans=q_spans)
+                                                  max_context_len=max_context_len, q_spans=q_spans,
+                                                  interp=interp)
     return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                       out, layer_idx, block_size, sm_scale, codec,
-                                      max_context_len=max_context_len, q_spans=q_spans)
+                                      max_context_len=max_context_len, q_spans=q_spans, interp=interp)
 
 
 def _conform(t, dtype):

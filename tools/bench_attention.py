@@ -19,6 +19,13 @@ call on the same rectangle and against the same work as separate calls: a
 uniform chunk call over the sequences with count == q_max plus a decode call
 over those with count == 1 (sequences with count 0 cost nothing there).
 
+--interp times the interpolating entry (kvecc_paged_attention_interp, Hamming(8,4)) in one
+process at --kv-heads and --heads / 4 cache heads, q_len 1 and 16, one JSON line per case:
+(a) the plain decode / chunk entry and the interpolating entry on the same clean encoded
+cache, which prices the first look; (b) the interpolating entry on caches injected at BER
+1e-3 and 1e-2, which prices the slow path; (c) shim_read_batch(interp=True) +
+repeat_interleave + masked SDPA on the BER 1e-3 cache, the path it replaces in the shim.
+
 --pkg DIR imports kvecc from DIR instead of this tree (the same measurement on
 another build, e.g. the parent commit's, in the same session).
 """
@@ -61,12 +68,15 @@ def main():
     ap.add_argument("--q-len", type=int, default=1, help="query tokens per sequence (1: one decode step)")
     ap.add_argument("--only", choices=["chunk"], default=None, help="--q-len > 1: time the chunk call alone")
     ap.add_argument("--q-spans", default=None, help="counts per sequence, right-aligned in --q-len tokens")
+    ap.add_argument("--interp", action="store_true", help="the interpolating entry against (a), (b), (c) above")
     ap.add_argument("--pkg", default=None, help="directory to import kvecc from (default: this tree)")
     args = ap.parse_args()
     if args.pkg:
         sys.path.insert(0, os.path.abspath(args.pkg))
     from kvecc import ops
     dev = torch.device("cuda:0")
+    if args.interp:
+        return bench_interp(args, ops, dev)
     g = torch.Generator(device=dev).manual_seed(0)
     nb = (args.ctx + args.bs - 1) // args.bs
     blocks = args.batch * nb
@@ -219,6 +229,91 @@ def main():
                       "achieved_gbs": gbs, "hbm_frac": gbs / 8000.0,
                       "data": data,
                       "includes": "split kernel + combine kernel + workspace alloc"}))
+
+
+def bench_interp(args, ops, dev):
+    import statistics
+    import time
+
+    import torch.nn.functional as F
+    from kvecc.memory_layout import kv_cache_pair
+    if args.codec != "hamming84":
+        raise SystemExit("--interp needs --codec hamming84")
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    sm = 1 / math.sqrt(args.d)
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 >= args.warmup_s:
+                break
+        passes = []
+        for _ in range(args.passes):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            passes.append(e0.elapsed_time(e1) / args.iters * 1e3)
+        return {"us_per_call": round(statistics.median(passes), 2), "pass_us": [round(x, 2) for x in passes],
+                "spread_us": round(max(passes) - min(passes), 2)}
+
+    for kvh in (args.kv_heads, max(1, args.heads // 4)):
+        x = torch.randint(0, 16, (2, blocks, 1, kvh, args.bs, args.d), device=dev, generator=g, dtype=torch.uint8)
+        caches = {}
+        for ber in (0.0, 1e-3, 1e-2):  # the same values under each error rate
+            kc, vc = kv_cache_pair((blocks, 1, kvh, args.bs * args.d), torch.uint8, dev)
+            for side, dst in enumerate((kc, vc)):
+                cw = ops.hamming84_encode(x[side].reshape(-1))
+                if ber > 0:
+                    ops.inject_into(cw, cw, ber, 8, seed=42 + side)
+                dst.view(-1).copy_(cw)
+            caches[ber] = (kc, vc)
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        groups = args.heads // kvh
+        for n in (1, 16):
+            qc = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half()
+            qt = qc.transpose(1, 2)
+            q1 = qc[:, :, 0].contiguous()
+            outc = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+            out1 = torch.empty_like(q1)
+            stats = ops.new_stats(dev)
+
+            def attend(ber, interp):
+                kc, vc = caches[ber]
+                if n == 1:
+                    return lambda: ops.paged_attention_into(q1, kc, vc, table, lens, ks, vs, out1, 0, args.bs, sm,
+                                                            "hamming84", args.ctx, interp=interp)
+                return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm,
+                                                              "hamming84", args.ctx, interp=interp)
+
+            def read_sdpa():
+                kc, vc = caches[1e-3]
+                k_t, v_t = ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, "hamming84", qc.dtype,
+                                               stats=stats, interp=True)
+                if groups > 1:
+                    k_t = k_t.repeat_interleave(groups, dim=1)
+                    v_t = v_t.repeat_interleave(groups, dim=1)
+                qpos = (lens - n).view(-1, 1, 1) + torch.arange(n, device=dev).view(1, n, 1)
+                mask = torch.arange(args.ctx, device=dev).view(1, 1, args.ctx) <= qpos
+                return F.scaled_dot_product_attention(qc, k_t, v_t, attn_mask=mask.unsqueeze(1))
+
+            res = {"plain_clean": timed(attend(0.0, False)), "interp_clean": timed(attend(0.0, True)),
+                   "interp_ber_1e-3": timed(attend(1e-3, True)), "interp_ber_1e-2": timed(attend(1e-2, True)),
+                   "read_interp_sdpa_ber_1e-3": timed(read_sdpa)}
+            print(json.dumps({"kernel": "paged_attention_interp", "batch": args.batch, "q_len": n,
+                              "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
+                              "block_size": args.bs, **res}), flush=True)
+        del caches, x
 
 
 if __name__ == "__main__":
