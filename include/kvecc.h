@@ -421,7 +421,28 @@ KVECC_API int kvecc_shim_read_batch(const void *k_cache, const void *v_cache, co
  * with no valid token (context_len <= 0 or only -1 blocks) gets the reference's
  * values: -8.0 in every lane for H84 (its kernel's -1e20 masking,
  * attention_ecc.py:342,391-423), 0 for Golay (reference_attention_ecc).  Query head h reads cache head h / (heads / kv_heads).  `workspace`:
- * kvecc_paged_attention_workspace(...) floats.  head_dim <= 256. */
+ * kvecc_paged_attention_workspace(...) floats.  head_dim <= 256.
+ *
+ * Byte caches without SECDED (no reference counterpart: the reference attends
+ * over Hamming(8,4) and Golay only).  kvecc_paged_attention,
+ * kvecc_paged_attention_chunk, kvecc_paged_attention_chunk_ragged and their
+ * kvecc_cpu_ twins also take KVECC_CODEC_H74 and KVECC_CODEC_NONE caches, which
+ * share H84's layout (uint8, one value per byte, rows of head_dim bytes).  A
+ * stored byte b is worth (data(b) - 8) * scale:
+ *   - H74:  data(b) is h74_decode4's nibble -- bit 7 is ignored and a double
+ *           error is miscorrected, as everywhere in the library;
+ *   - NONE: data(b) = b & 0xF.
+ * Everything else follows H84's rules: head_dim % 4 == 0 and head_dim <= 256,
+ * the query dtypes, the GQA map, -1 blocks, the max_context_len clamp, and the
+ * empty value, -8.0 in every lane (the kernels share H84's body, and no
+ * reference defines another value for these codecs).  The launch geometry is
+ * H84's at the same shape, so a clean cache of either codec returns the bits
+ * an H84 cache of the same nibbles returns.  The workspace functions are
+ * unchanged.  kvecc_paged_attention_interp keeps rejecting everything but H84.
+ * A deliberate difference: kvecc_shim_read dequantizes a NONE byte raw (all 8
+ * bits, unmasked), the attention kernels read its low nibble.  The two agree on
+ * every byte the write, the 4-bit injection and a 4-bit ageing can produce
+ * (b < 16) and differ only on bytes nothing in the library stores. */
 KVECC_API int64_t kvecc_paged_attention_workspace(int64_t batch, int64_t heads, int64_t head_dim,
                                                   int64_t max_context_len);
 KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *k_cache,

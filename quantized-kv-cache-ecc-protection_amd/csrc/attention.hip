@@ -4,7 +4,9 @@
 // causal: a prefill, a chunk, a verify step's draft tokens; no reference
 // counterpart), and kvecc_paged_attention_interp (the chunk form over a
 // Hamming(8,4) cache with detected double errors interpolated from the
-// neighbouring tokens, in kernels of its own).  The chunked entry runs the same kernel bodies (attn_*_body.inc)
+// neighbouring tokens, in kernels of its own).  Hamming(7,4) and unprotected INT4
+// caches (no reference counterpart) run a sibling family of the Hamming(8,4)
+// kernels with another decode table (ByteAttnArgs).  The chunked entry runs the same kernel bodies (attn_*_body.inc)
 // under kernel names of its own: the matrix-core kernels with 16 (token, head)
 // columns per workgroup and a per-column key limit (ChunkMap), the split
 // kernels over a virtual batch of batch * q_len rows (ChunkArgs).
@@ -170,6 +172,50 @@ constexpr bool is_chunk = std::is_base_of<ChunkArgs, A>::value;
 struct InterpArgs : RaggedArgs {};
 template <typename A>
 constexpr bool is_interp = std::is_same<A, InterpArgs>::value;
+
+// Byte caches without SECDED (KVECC_CODEC_H74, KVECC_CODEC_NONE: Hamming(8,4)'s
+// layout, uint8, one value per byte, rows of head_dim bytes) run one sibling
+// family of kernels, of their own names, over the Hamming(8,4) bodies: every
+// H(8,4) kernel decodes through a 256-entry table that its workgroup fills, so
+// the codec is the table.  The family's argument blocks add the table selector
+// behind AttnArgs / RaggedArgs -- every other kernel keeps its block, its text
+// and its registers -- and the selector is read once per workgroup, where the
+// table is staged (byte_table_nibble: a uniform branch outside every loop).
+// One family instead of a CODEC template value per codec: one new instantiation
+// set, not two, and an instruction stream per shape that is Hamming(8,4)'s.
+struct ByteAttnArgs : AttnArgs {
+  uint32_t tab;  // KVECC_CODEC_H74 or KVECC_CODEC_NONE
+};
+struct ByteChunkArgs : RaggedArgs {
+  uint32_t tab;
+};
+// The uniform matrix-core chunk kernels' block: the selector behind ChunkArgs, not
+// behind RaggedArgs, for the reason Hamming(8,4)'s uniform kernels keep ChunkArgs
+// (see RaggedArgs; profiles/byte_attention has this family's measurement).
+struct ByteUniformArgs : ChunkArgs {
+  uint32_t tab;
+};
+template <typename A>
+constexpr bool is_byte = std::is_same<A, ByteAttnArgs>::value || std::is_same<A, ByteChunkArgs>::value ||
+                         std::is_same<A, ByteUniformArgs>::value;
+
+// Entry b of a workgroup's decode table, as a nibble: data(b) of kvecc.h's
+// attention contract.  Hamming(8,4): single errors corrected, doubles keep their
+// data.  The byte family: Hamming(7,4) -- bit 7 ignored, doubles miscorrected,
+// as h74_decode4 does everywhere -- or the low nibble of an unprotected byte.
+template <typename A>
+__device__ __forceinline__ uint32_t byte_table_nibble(const A &a, uint32_t b) {
+  if constexpr (is_byte<A>) {
+    if (a.tab == KVECC_CODEC_NONE) return b & 0xFu;
+    uint32_t q, f, n = 0;
+    h74_decode4(b, q, f, n);
+    return q & 0xFu;
+  } else {
+    uint32_t q, t, n1 = 0, n2 = 0;
+    h84_decode4(b, q, t, n1, n2);
+    return q & 0xFu;
+  }
+}
 
 // The first look of the interpolating kernels: bit 3 of each byte that is a
 // type-2 codeword (double detected: syndrome != 0, overall parity even) -- the
@@ -584,6 +630,22 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_interp_kernel(InterpA
 #include "attn_split_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the byte family's general path (KVECC_CODEC_H74 / KVECC_CODEC_NONE caches): the Hamming(8,4)
+// instantiations of the same body, the table by the argument block's selector
+template <typename T, int VEC, int W, bool BUF, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_byte_kernel(ByteAttnArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+#define ATTN_BODY_CHUNK 0
+#include "attn_split_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <typename T, int VEC, int W, bool BUF, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_byte_chunk_kernel(ByteChunkArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+#define ATTN_BODY_CHUNK 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_CHUNK
+}
 
 // ---- GQA on the matrix cores (Hamming(8,4), fp16 queries) -----------------------
 //
@@ -771,6 +833,29 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_interp_kernel(I
   using ChunkMap = ChunkMapT<RaggedArgs>;
 #include "attn_h84_mfma_interp_body.inc"
 }
+// the byte family's: the decode, chunk and ragged kernels over the same body
+template <int D, int G>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_byte_mfma_kernel(ByteAttnArgs a) {
+#define ATTN_BODY_CHUNK 0
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_byte_mfma_chunk_kernel(ByteUniformArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<ChunkArgs>;
+#define ATTN_BODY_CHUNK 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_byte_mfma_ragged_kernel(ByteChunkArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
 
 // ---- GQA on the matrix cores, Golay(24,12) int32 caches, head_dim 128 ---------
 //
@@ -833,7 +918,12 @@ static int pow2_at_least(int64_t x) {
 // chunked call's over its virtual batch (ChunkArgs)
 #define KVECC_SPLIT_LAUNCH(VEC_, WW, BUF_, G_)                                                                  \
   do {                                                                                                          \
-    if constexpr (is_interp<A>) {                                                                               \
+    if constexpr (is_byte<A>) {                                                                                 \
+      if constexpr (CODEC == KVECC_CODEC_H84 && is_chunk<A>)                                                    \
+        KVECC_LAUNCH((paged_attn_split_byte_chunk_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
+      else if constexpr (CODEC == KVECC_CODEC_H84)                                                              \
+        KVECC_LAUNCH((paged_attn_split_byte_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
+    } else if constexpr (is_interp<A>) {                                                                        \
       if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                           \
         KVECC_LAUNCH((paged_attn_split_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
     } else if constexpr (is_chunk<A>)                                                                           \
@@ -932,16 +1022,25 @@ static int launch_attn(const A &a, int64_t batch, int gq, hipStream_t st, bool c
   return KVECC_OK;
 }
 
-template <int D>
-static int launch_mfma_d(const AttnArgs &a, int64_t batch, int gm, hipStream_t st) {
+// (A: AttnArgs, or ByteAttnArgs for the byte family's kernels)
+template <int D, typename A>
+static int launch_mfma_d(const A &a, int64_t batch, int gm, hipStream_t st) {
   const dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gm));
+#define KVECC_MFMA_LAUNCH(G_)                                                                \
+  do {                                                                                       \
+    if constexpr (is_byte<A>)                                                                \
+      KVECC_LAUNCH((paged_attn_byte_mfma_kernel<D, G_>), grid, dim3(kBlock), 0, st, a);      \
+    else                                                                                     \
+      KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, G_>), grid, dim3(kBlock), 0, st, a);       \
+  } while (0)
   switch (gm) {
-    case 1: KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, 1>), grid, dim3(kBlock), 0, st, a); break;
-    case 2: KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, 2>), grid, dim3(kBlock), 0, st, a); break;
-    case 4: KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, 4>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, 8>), grid, dim3(kBlock), 0, st, a); break;
-    default: KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, 16>), grid, dim3(kBlock), 0, st, a); break;
+    case 1: KVECC_MFMA_LAUNCH(1); break;
+    case 2: KVECC_MFMA_LAUNCH(2); break;
+    case 4: KVECC_MFMA_LAUNCH(4); break;
+    case 8: KVECC_MFMA_LAUNCH(8); break;
+    default: KVECC_MFMA_LAUNCH(16); break;
   }
+#undef KVECC_MFMA_LAUNCH
   if (!a.ctr) launch_combine<__half>(a, batch, st);
   return KVECC_OK;
 }
@@ -964,6 +1063,14 @@ static int launch_mfma(int codec, const AttnArgs &a, int64_t batch, int gm, hipS
     if (codec == KVECC_CODEC_GOLAY_PACKED) return launch_golay_mfma<true>(a, batch, gm, st);
     return launch_golay_mfma<false>(a, batch, gm, st);
   }
+  switch (a.d) {
+    case 32: return launch_mfma_d<32>(a, batch, gm, st);
+    case 64: return launch_mfma_d<64>(a, batch, gm, st);
+    default: return launch_mfma_d<128>(a, batch, gm, st);
+  }
+}
+// the byte family's decode kernels (Hamming(8,4)'s domain and geometry)
+static int launch_byte_mfma(const ByteAttnArgs &a, int64_t batch, int gm, hipStream_t st) {
   switch (a.d) {
     case 32: return launch_mfma_d<32>(a, batch, gm, st);
     case 64: return launch_mfma_d<64>(a, batch, gm, st);
@@ -1070,6 +1177,29 @@ static int launch_mfma_chunk(int codec, const RaggedArgs &a, int64_t batch, int6
   return KVECC_OK;
 }
 
+// the byte family's matrix-core chunk kernels: the ragged entry's or the uniform ones
+static int launch_byte_mfma_chunk(const ByteChunkArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
+  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
+  if (a.q_spans) {
+    switch (a.d) {
+      case 32: KVECC_LAUNCH((paged_attn_byte_mfma_ragged_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
+      case 64: KVECC_LAUNCH((paged_attn_byte_mfma_ragged_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
+      default: KVECC_LAUNCH((paged_attn_byte_mfma_ragged_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
+    }
+  } else {
+    ByteUniformArgs u;  // the uniform kernels' argument block
+    static_cast<ChunkArgs &>(u) = a;
+    u.tab = a.tab;
+    switch (a.d) {
+      case 32: KVECC_LAUNCH((paged_attn_byte_mfma_chunk_kernel<32>), grid, dim3(kBlock), 0, st, u); break;
+      case 64: KVECC_LAUNCH((paged_attn_byte_mfma_chunk_kernel<64>), grid, dim3(kBlock), 0, st, u); break;
+      default: KVECC_LAUNCH((paged_attn_byte_mfma_chunk_kernel<128>), grid, dim3(kBlock), 0, st, u); break;
+    }
+  }
+  launch_combine<__half>(a, batch * a.q_len, st);
+  return KVECC_OK;
+}
+
 // the interpolating entry's matrix-core kernels (uniform calls too: the spans are nullable)
 static int launch_mfma_interp(const InterpArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
   const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
@@ -1082,8 +1212,9 @@ static int launch_mfma_interp(const InterpArgs &a, int64_t batch, int64_t tiles,
   return KVECC_OK;
 }
 // ... and its general path: launch_codec_rows for the interpolating split kernels
-template <typename T>
-static int launch_interp_rows(InterpArgs a, int64_t rows, int gq, hipStream_t st) {
+// (A InterpArgs) and for the byte family's (A ByteChunkArgs)
+template <typename T, typename A>
+static int launch_h84_rows(A a, int64_t rows, int gq, hipStream_t st) {
   const int64_t wg_per_row = a.heads / gq;
   if (rows * wg_per_row <= kMaxGridY) return launch_attn<T, KVECC_CODEC_H84>(a, rows, gq, st);
   const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
@@ -1142,10 +1273,17 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
                      (long long)heads, (long long)kv_heads);
   if (head_dim < 1 || head_dim > kAttnMaxD)
     return set_error(KVECC_EINVAL, "paged_attention: head_dim %lld not in [1, %d]", (long long)head_dim, kAttnMaxD);
-  if (codec != KVECC_CODEC_H84 && codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL, "paged_attention: codec %d (hamming84 or golay only)", codec);
+  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
+      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL, "paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed only)",
+                     codec);
+  // the byte family (kvecc.h): Hamming(8,4)'s layout, rules and launch geometry, its own kernels
+  const bool bytes = codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74;
+  const int table = codec;
+  if (bytes) codec = KVECC_CODEC_H84;
   if (codec == KVECC_CODEC_H84 && head_dim % 4 != 0)
-    return set_error(KVECC_EINVAL, "paged_attention: hamming84 head_dim must be a multiple of 4");
+    return set_error(KVECC_EINVAL, "paged_attention: %s head_dim must be a multiple of 4",
+                     table == KVECC_CODEC_NONE ? "int4" : table == KVECC_CODEC_H74 ? "hamming74" : "hamming84");
   if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
     return set_error(KVECC_EINVAL, "paged_attention: bad cache geometry");
   if (num_blocks < 1 || num_blocks * num_layers * kv_heads * block_size > 0x7FFFFFFFLL)
@@ -1158,7 +1296,8 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
   if (workspace_floats < need)
     return set_error(KVECC_EINVAL, "paged_attention: workspace %lld < %lld floats",
                      (long long)workspace_floats, (long long)need);
-  AttnArgs a;
+  ByteAttnArgs a;  // AttnArgs for every other codec's kernels
+  a.tab = (uint32_t)table;
   a.q = query;
   a.k_cache = k_cache;
   a.v_cache = v_cache;
@@ -1224,15 +1363,26 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
   }
   hipStream_t st = as_stream(stream);
   if (gm) {
-    const int rc = launch_mfma(codec, a, batch, gm, st);
+    const int rc = bytes ? launch_byte_mfma(a, batch, gm, st) : launch_mfma(codec, a, batch, gm, st);
     if (rc != KVECC_OK) return rc;
     return check_launch("paged_attention");
   }
   int rc;
+  if (bytes) {
+    switch (q_dtype) {
+      case KVECC_F32: rc = launch_attn<float, KVECC_CODEC_H84>(a, batch, gq, st); break;
+      case KVECC_F16: rc = launch_attn<__half, KVECC_CODEC_H84>(a, batch, gq, st); break;
+      case KVECC_BF16: rc = launch_attn<__hip_bfloat16, KVECC_CODEC_H84>(a, batch, gq, st); break;
+      default: return set_error(KVECC_EINVAL, "paged_attention: bad dtype %d", q_dtype);
+    }
+    if (rc != KVECC_OK) return rc;
+    return check_launch("paged_attention");
+  }
+  const AttnArgs &o = a;  // every other codec's argument block
   switch (q_dtype) {
-    case KVECC_F32: rc = launch_codec<float>(codec, a, batch, gq, st); break;
-    case KVECC_F16: rc = launch_codec<__half>(codec, a, batch, gq, st); break;
-    case KVECC_BF16: rc = launch_codec<__hip_bfloat16>(codec, a, batch, gq, st); break;
+    case KVECC_F32: rc = launch_codec<float>(codec, o, batch, gq, st); break;
+    case KVECC_F16: rc = launch_codec<__half>(codec, o, batch, gq, st); break;
+    case KVECC_BF16: rc = launch_codec<__hip_bfloat16>(codec, o, batch, gq, st); break;
     default: return set_error(KVECC_EINVAL, "paged_attention: bad dtype %d", q_dtype);
   }
   if (rc != KVECC_OK) return rc;
@@ -1298,10 +1448,17 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   if (head_dim < 1 || head_dim > kAttnMaxD)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: head_dim %lld not in [1, %d]", (long long)head_dim,
                      kAttnMaxD);
-  if (codec != KVECC_CODEC_H84 && codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: codec %d (hamming84 or golay only)", codec);
+  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
+      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL,
+                     "paged_attention_chunk: codec %d (int4, hamming74, hamming84, golay or golay_packed only)", codec);
+  // the byte family (kvecc.h): Hamming(8,4)'s layout, rules and launch geometry, its own kernels
+  const bool bytes = codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74;
+  const int table = codec;
+  if (bytes) codec = KVECC_CODEC_H84;
   if (codec == KVECC_CODEC_H84 && head_dim % 4 != 0)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: hamming84 head_dim must be a multiple of 4");
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: %s head_dim must be a multiple of 4",
+                     table == KVECC_CODEC_NONE ? "int4" : table == KVECC_CODEC_H74 ? "hamming74" : "hamming84");
   if (q_dtype != KVECC_F32 && q_dtype != KVECC_F16 && q_dtype != KVECC_BF16)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: bad dtype %d", q_dtype);
   if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
@@ -1320,7 +1477,8 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   if (workspace_floats < need)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: workspace %lld < %lld floats",
                      (long long)workspace_floats, (long long)need);
-  InterpArgs a;  // RaggedArgs for every other entry's kernels
+  ByteChunkArgs a;  // RaggedArgs for every other codec's kernels (the interpolating ones: a copy, below)
+  a.tab = (uint32_t)table;
   a.q = query;
   a.k_cache = k_cache;
   a.v_cache = v_cache;
@@ -1408,13 +1566,25 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   }
   hipStream_t st = as_stream(stream);
   int rc;
-  if (interp && gm) {
-    rc = launch_mfma_interp(a, batch, tiles, st);
-  } else if (interp) {
+  if (interp) {
+    InterpArgs ia;  // the interpolating kernels' argument block
+    static_cast<RaggedArgs &>(ia) = a;
+    if (gm) {
+      rc = launch_mfma_interp(ia, batch, tiles, st);
+    } else {
+      switch (q_dtype) {
+        case KVECC_F32: rc = launch_h84_rows<float>(ia, vbatch, gq, st); break;
+        case KVECC_F16: rc = launch_h84_rows<__half>(ia, vbatch, gq, st); break;
+        default: rc = launch_h84_rows<__hip_bfloat16>(ia, vbatch, gq, st); break;
+      }
+    }
+  } else if (bytes && gm) {
+    rc = launch_byte_mfma_chunk(a, batch, tiles, st);
+  } else if (bytes) {
     switch (q_dtype) {
-      case KVECC_F32: rc = launch_interp_rows<float>(a, vbatch, gq, st); break;
-      case KVECC_F16: rc = launch_interp_rows<__half>(a, vbatch, gq, st); break;
-      default: rc = launch_interp_rows<__hip_bfloat16>(a, vbatch, gq, st); break;
+      case KVECC_F32: rc = launch_h84_rows<float>(a, vbatch, gq, st); break;
+      case KVECC_F16: rc = launch_h84_rows<__half>(a, vbatch, gq, st); break;
+      default: rc = launch_h84_rows<__hip_bfloat16>(a, vbatch, gq, st); break;
     }
   } else if (gm) {
     rc = launch_mfma_chunk(codec, a, batch, tiles, st);

@@ -82,11 +82,8 @@
       rows[i] = row;
     }
   }
-  {
-    uint32_t dq, dt, n1 = 0, n2 = 0;
-    h84_decode4(threadIdx.x, dq, dt, n1, n2);  // kBlock == 256: one table entry per thread
-    lut[threadIdx.x] = (uint8_t)(dq & 0xFu);
-  }
+  // kBlock == 256: one table entry per thread (the byte family's kernels: their codec's table)
+  lut[threadIdx.x] = (uint8_t)byte_table_nibble(a, threadIdx.x);
   float qsum = 0.0f;  // sum of head n's query over all d (the offset fold)
 #pragma unroll
   for (int kk = 0; kk < KK; ++kk)

@@ -137,11 +137,8 @@
       dst[512 + i] = src1[i];
     }
   }
-  if (CODEC == KVECC_CODEC_H84 && threadIdx.x < 256) {
-    uint32_t q, t, n1 = 0, n2 = 0;
-    h84_decode4(threadIdx.x, q, t, n1, n2);
-    lut[threadIdx.x] = (h84_lut_t)((int)(q & 0xFu) - 8);
-  }
+  if (CODEC == KVECC_CODEC_H84 && threadIdx.x < 256)  // (the byte family's kernels: their codec's table)
+    lut[threadIdx.x] = (h84_lut_t)((int)byte_table_nibble(a, threadIdx.x) - 8);
   float qsum[G];  // sum of this lane's q (folds the decode's kOffset out of the K sums)
 #pragma unroll
   for (int j = 0; j < G; ++j) {

@@ -1027,8 +1027,13 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
   if (kv_heads < 1 || heads % kv_heads != 0)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: heads not a multiple of kv heads");
   if (head_dim < 1) return set_error(KVECC_EINVAL, "cpu_paged_attention: empty head_dim");
-  if (codec != KVECC_CODEC_H84 && codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: codec %d (hamming84 or golay only)", codec);
+  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
+      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL,
+                     "cpu_paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed only)", codec);
+  if ((codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74) && head_dim % 4 != 0)  // as the device entries
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: %s head_dim must be a multiple of 4",
+                     codec == KVECC_CODEC_NONE ? "int4" : "hamming74");
   if (q_dtype < KVECC_F32 || q_dtype > KVECC_BF16)
     return set_error(KVECC_EINVAL, "cpu_paged_attention: bad dtype %d", q_dtype);
   if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
@@ -1069,8 +1074,15 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
       } else {
         const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * head_dim;
         for (int64_t j = 0; j < head_dim; ++j) {
-          uint32_t d, t, n1 = 0, n2 = 0;
-          h84_decode4(c[j], d, t, n1, n2);
+          uint32_t d, t = 0, n1 = 0, n2 = 0;
+          if (codec == KVECC_CODEC_NONE) {  // an unprotected byte's low nibble
+            d = c[j] & 0xFu;
+          } else if (codec == KVECC_CODEC_H74) {  // bit 7 ignored, doubles miscorrected
+            h74_decode4(c[j], d, t, n1);
+            d &= 0xFu;
+          } else {
+            h84_decode4(c[j], d, t, n1, n2);
+          }
           if (cl) {  // a double becomes the rounded mean of its neighbours' decoded values
             uint32_t dl, dr, tt;
             h84_decode4(cl[j], dl, tt, n1, n2);

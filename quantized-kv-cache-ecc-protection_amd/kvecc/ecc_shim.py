@@ -125,6 +125,16 @@ class ECCShimConfig:
     is read.  It keeps no statistics either.  Each sequence's last token clamps
     at its own length, where the batched read interpolates a shorter sequence's
     last token against the zero row past it.
+    ``kernel_attention`` (append mode, hamming74 or int4 only, opt-in) sends
+    every forward of those two codecs through the paged attention kernels when
+    decode_stats is off and head_dim <= 256: single-token steps to the decode
+    entry, forwards of more than one token to the chunked causal entry, held
+    spans to the ragged entry, the query read in place.  It is a flag, where
+    hamming84 and golay decode steps take the kernel by default, because these
+    two codecs count decode statistics on every forward today: with the flag
+    on NO decode statistics are kept (``chunk_attention`` alone leaves these
+    codecs on the read + SDPA path).  For hamming74, scrub_ecc_cache still
+    supplies the counts; int4 has nothing to count.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -135,7 +145,7 @@ class ECCShimConfig:
     def __init__(self, codec="hamming84", ber=0.0, block_size=16, num_blocks=256,
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
-                 decode_stats=False, chunk_attention=False, interp_attention=False):
+                 decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -168,6 +178,11 @@ class ECCShimConfig:
             raise ValueError("interp_attention=True needs cache_mode='append', codec='hamming84' and "
                              "use_interpolation=True")
         self.interp_attention = bool(interp_attention)
+        if kernel_attention and (cache_mode != "append" or codec not in ("hamming74", "int4")):
+            raise ValueError("kernel_attention=True needs cache_mode='append' and codec 'hamming74' or 'int4' "
+                             f"(hamming84 and golay take the kernels by default), not codec={codec!r}, "
+                             f"cache_mode={cache_mode!r}")
+        self.kernel_attention = bool(kernel_attention)
 
 
 class SimpleBlockManager:
@@ -647,8 +662,9 @@ class ECCBackend:
             return torch.zeros_like(q)
         table, dev_lens = mgr.block_table[:b], mgr.ctx_lens[layer_idx, :b]
         interp = cfg.use_interpolation and cfg.codec == "hamming84"
-        if q_len == 1 and cfg.codec in ("hamming84", "golay") and not interp and not cfg.decode_stats \
-                and d <= 256:
+        # hamming74 / int4 take the kernels only under kernel_attention (their codec is checked there)
+        kernel_codec = cfg.codec in ("hamming84", "golay") or cfg.kernel_attention
+        if q_len == 1 and kernel_codec and not interp and not cfg.decode_stats and d <= 256:
             # decode step: paged attention with inline decode over the ragged
             # tables; no statistics, as on the reference's seq_len == 1 path
             q1 = q[:, :, 0, :].contiguous()
@@ -681,8 +697,8 @@ class ECCBackend:
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx, q_spans=spans,
                 interp=True)
             return out.transpose(1, 2)
-        if q_len > 1 and cfg.chunk_attention and cfg.codec in ("hamming84", "golay") and not interp \
-                and not cfg.decode_stats and d <= 256:
+        chunk_kernel = cfg.kernel_attention or (cfg.chunk_attention and cfg.codec in ("hamming84", "golay"))
+        if q_len > 1 and chunk_kernel and not interp and not cfg.decode_stats and d <= 256:
             # prefill / chunk / verify step on the chunked causal kernel: q read
             # in place as [batch, q_len, heads, d], no dense K / V, no statistics
             qt = q.transpose(1, 2)

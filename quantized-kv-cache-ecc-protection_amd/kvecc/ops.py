@@ -1075,9 +1075,13 @@ def check_scrub_stats(stats, device):
 # Paged decode attention with inline ECC decode
 # ============================================================================
 
-_ATTN_ROW_WORDS = {"hamming84": lambda d: d, "golay": lambda d: (d + 2) // 3,
+# (int4 and hamming74: Hamming(8,4)'s layout, one value per byte -- kvecc.h "byte caches")
+_ATTN_ROW_WORDS = {"int4": lambda d: d, "hamming74": lambda d: d,
+                   "hamming84": lambda d: d, "golay": lambda d: (d + 2) // 3,
                    "golay_packed": lambda d: (3 * ((d + 2) // 3) + 3) // 4 * 4}  # KVECC_GOLAY_PACKED_ROW
-_ATTN_CACHE_DT = {"hamming84": torch.uint8, "golay": torch.int32, "golay_packed": torch.uint8}
+_ATTN_CACHE_DT = {"int4": torch.uint8, "hamming74": torch.uint8,
+                  "hamming84": torch.uint8, "golay": torch.int32, "golay_packed": torch.uint8}
+_ATTN_CODEC_NAMES = "int4, hamming74, hamming84, golay or golay_packed"
 _attn_ws = {}  # (device index, stream) -> float32 workspace, grown on demand
 _attn_ws_retired = []  # outgrown workspaces stay alive: a captured HIP graph may still name them
 
@@ -1096,7 +1100,7 @@ def _attn_workspace(device, n):
 def _check_attention_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                           out, block_size, codec):
     if codec not in _ATTN_CACHE_DT:
-        raise ValueError(f"paged attention codec {codec!r} (hamming84, golay or golay_packed)")
+        raise ValueError(f"paged attention codec {codec!r} ({_ATTN_CODEC_NAMES})")
     if query.dim() != 3 or query.dtype not in _DT:
         raise ValueError(f"query must be [B, H, D] fp32/fp16/bf16, got {tuple(query.shape)} {query.dtype}")
     batch, heads, head_dim = query.shape
@@ -1138,7 +1142,7 @@ def _check_attention_rest(batch, heads, head_dim, device, k_cache, v_cache, bloc
     geometry against the codec and block_size, table and lengths against the
     batch, one device, contiguity."""
     if codec not in _ATTN_CACHE_DT:
-        raise ValueError(f"paged attention codec {codec!r} (hamming84, golay or golay_packed)")
+        raise ValueError(f"paged attention codec {codec!r} ({_ATTN_CODEC_NAMES})")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
         raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
     nb, nl, kvh, row = k_cache.shape

@@ -26,6 +26,12 @@ cache, which prices the first look; (b) the interpolating entry on caches inject
 1e-3 and 1e-2, which prices the slow path; (c) shim_read_batch(interp=True) +
 repeat_interleave + masked SDPA on the BER 1e-3 cache, the path it replaces in the shim.
 
+--bytes times the byte family against Hamming(8,4) in one process at --kv-heads and --heads / 4
+cache heads, q_len 1 and 16, one JSON line per case, every pass visiting the cases in turn: int4,
+hamming74 and hamming84 on clean encoded caches of the same nibbles, hamming74 and hamming84
+injected at BER 1e-3, and shim_read_batch + repeat_interleave + masked SDPA over the int4 and
+hamming74 caches, the path ECCShimConfig(kernel_attention=True) replaces.
+
 --pkg DIR imports kvecc from DIR instead of this tree (the same measurement on
 another build, e.g. the parent commit's, in the same session).
 """
@@ -44,9 +50,20 @@ sys.path.insert(0, os.path.join(REPO, "quantized-kv-cache-ecc-protection_amd"))
 import torch  # noqa: E402
 
 
+# codecs with Hamming(8,4)'s cache layout (one value per byte) -> bits per stored word, for injection
+BYTE_CODECS = {"int4": 4, "hamming74": 7, "hamming84": 8}
+
+
+def byte_encode(ops, codec, nibbles):
+    if codec == "int4":
+        return nibbles.clone()
+    return ops.hamming74_encode(nibbles) if codec == "hamming74" else ops.hamming84_encode(nibbles)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--codec", default="hamming84")
+    ap.add_argument("--codec", default="hamming84",
+                    help="hamming84, golay, golay_packed, hamming74 or int4")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--heads", type=int, default=32)
     ap.add_argument("--kv-heads", type=int, default=32)
@@ -69,6 +86,8 @@ def main():
     ap.add_argument("--only", choices=["chunk"], default=None, help="--q-len > 1: time the chunk call alone")
     ap.add_argument("--q-spans", default=None, help="counts per sequence, right-aligned in --q-len tokens")
     ap.add_argument("--interp", action="store_true", help="the interpolating entry against (a), (b), (c) above")
+    ap.add_argument("--bytes", action="store_true",
+                    help="the byte family (int4, hamming74) beside hamming84, alternated in one process")
     ap.add_argument("--pkg", default=None, help="directory to import kvecc from (default: this tree)")
     args = ap.parse_args()
     if args.pkg:
@@ -77,26 +96,29 @@ def main():
     dev = torch.device("cuda:0")
     if args.interp:
         return bench_interp(args, ops, dev)
+    if args.bytes:
+        return bench_bytes(args, ops, dev)
     g = torch.Generator(device=dev).manual_seed(0)
     nb = (args.ctx + args.bs - 1) // args.bs
     blocks = args.batch * nb
-    per = args.d if args.codec == "hamming84" else (args.d + 2) // 3
+    per = args.d if args.codec in BYTE_CODECS else (args.d + 2) // 3
     if args.codec == "golay_packed":  # bytes per token row (KVECC_GOLAY_PACKED_ROW)
         per = (3 * per + 3) // 4 * 4
     from kvecc.memory_layout import kv_cache_pair  # K/V as SimpleBlockManager lays them out
     kc, vc = kv_cache_pair((blocks, 1, args.kv_heads, args.bs * per),
                            torch.int32 if args.codec == "golay" else torch.uint8, dev)
     if args.data == "random":
-        kc.random_(0, 1 << 24 if args.codec == "golay" else 256, generator=g)
+        # (int4: the bytes a cache can hold, b < 16)
+        kc.random_(0, 1 << 24 if args.codec == "golay" else 16 if args.codec == "int4" else 256, generator=g)
         vc.copy_(kc.roll(1, 0))
     else:
-        ber = args.ber if args.ber is not None else (1e-3 if args.codec == "hamming84" else 1e-2)
+        ber = args.ber if args.ber is not None else (1e-3 if args.codec in BYTE_CODECS else 1e-2)
         for side, dst in enumerate((kc, vc)):
             x = torch.randint(0, 16, (blocks, 1, args.kv_heads, args.bs, args.d), device=dev, generator=g,
                               dtype=torch.uint8)
-            if args.codec == "hamming84":
-                cw = ops.hamming84_encode(x.view(-1))
-                ops.inject_into(cw, cw, ber, 8, seed=42 + side)
+            if args.codec in BYTE_CODECS:
+                cw = byte_encode(ops, args.codec, x.view(-1))
+                ops.inject_into(cw, cw, ber, BYTE_CODECS[args.codec], seed=42 + side)
                 dst.view(-1).copy_(cw)
             else:
                 gg = (args.d + 2) // 3
@@ -311,6 +333,101 @@ def bench_interp(args, ops, dev):
                    "interp_ber_1e-3": timed(attend(1e-3, True)), "interp_ber_1e-2": timed(attend(1e-2, True)),
                    "read_interp_sdpa_ber_1e-3": timed(read_sdpa)}
             print(json.dumps({"kernel": "paged_attention_interp", "batch": args.batch, "q_len": n,
+                              "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
+                              "block_size": args.bs, **res}), flush=True)
+        del caches, x
+
+
+def bench_bytes(args, ops, dev):
+    import statistics
+    import time
+
+    import torch.nn.functional as F
+    from kvecc.memory_layout import kv_cache_pair
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    sm = 1 / math.sqrt(args.d)
+
+    def timed_alternating(cases):
+        """Every case warmed up, then --passes rounds that visit the cases in turn."""
+        for fn in cases.values():
+            t0 = time.perf_counter()
+            while True:
+                for _ in range(args.warmup):
+                    fn()
+                torch.cuda.synchronize()
+                if time.perf_counter() - t0 >= args.warmup_s:
+                    break
+        passes = {name: [] for name in cases}
+        for _ in range(args.passes):
+            for name, fn in cases.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                passes[name].append(e0.elapsed_time(e1) / args.iters * 1e3)
+        return {name: {"us_per_call": round(statistics.median(p), 2), "pass_us": [round(x, 2) for x in p],
+                       "spread_us": round(max(p) - min(p), 2)} for name, p in passes.items()}
+
+    for kvh in (args.kv_heads, max(1, args.heads // 4)):
+        x = torch.randint(0, 16, (2, blocks, 1, kvh, args.bs, args.d), device=dev, generator=g, dtype=torch.uint8)
+        caches = {}
+        for codec, ber in (("int4", 0.0), ("hamming74", 0.0), ("hamming84", 0.0), ("hamming74", 1e-3),
+                           ("hamming84", 1e-3)):
+            kc, vc = kv_cache_pair((blocks, 1, kvh, args.bs * args.d), torch.uint8, dev)
+            for side, dst in enumerate((kc, vc)):
+                cw = byte_encode(ops, codec, x[side].reshape(-1))
+                if ber > 0:
+                    ops.inject_into(cw, cw, ber, BYTE_CODECS[codec], seed=42 + side)
+                dst.view(-1).copy_(cw)
+            caches[codec, ber] = (kc, vc)
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        groups = args.heads // kvh
+        for n in (1, 16):
+            qc = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half()
+            qt = qc.transpose(1, 2)
+            q1 = qc[:, :, 0].contiguous()
+            outc = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+            out1 = torch.empty_like(q1)
+            stats = ops.new_stats(dev)
+
+            def attend(codec, ber):
+                kc, vc = caches[codec, ber]
+                if n == 1:
+                    return lambda: ops.paged_attention_into(q1, kc, vc, table, lens, ks, vs, out1, 0, args.bs, sm,
+                                                            codec, args.ctx)
+                return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm,
+                                                              codec, args.ctx)
+
+            def read_sdpa(codec):
+                kc, vc = caches[codec, 0.0]
+
+                def fn():
+                    k_t, v_t = ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, codec, qc.dtype,
+                                                   stats=stats, interp=False)
+                    if groups > 1:
+                        k_t = k_t.repeat_interleave(groups, dim=1)
+                        v_t = v_t.repeat_interleave(groups, dim=1)
+                    qpos = (lens - n).view(-1, 1, 1) + torch.arange(n, device=dev).view(1, n, 1)
+                    mask = torch.arange(args.ctx, device=dev).view(1, 1, args.ctx) <= qpos
+                    return F.scaled_dot_product_attention(qc, k_t, v_t, attn_mask=mask.unsqueeze(1))
+                return fn
+
+            kernels = {"int4_clean": attend("int4", 0.0), "hamming74_clean": attend("hamming74", 0.0),
+                       "hamming84_clean": attend("hamming84", 0.0), "hamming74_ber_1e-3": attend("hamming74", 1e-3),
+                       "hamming84_ber_1e-3": attend("hamming84", 1e-3)}
+            res = timed_alternating(kernels)
+            res.update(timed_alternating({"int4_read_sdpa": read_sdpa("int4"),
+                                          "hamming74_read_sdpa": read_sdpa("hamming74")}))
+            res["hamming84_minus_int4_us"] = round(res["hamming84_clean"]["us_per_call"] -
+                                                   res["int4_clean"]["us_per_call"], 2)
+            print(json.dumps({"kernel": "paged_attention_bytes", "batch": args.batch, "q_len": n,
                               "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
                               "block_size": args.bs, **res}), flush=True)
         del caches, x
