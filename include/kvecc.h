@@ -548,6 +548,66 @@ KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_st
                                            int64_t max_context_len, float sm_scale, int codec,
                                            float *workspace, int64_t workspace_floats, void *stream);
 
+/* ---- Counted attention ------------------------------------------------------- */
+/* Paged attention over a Hamming(8,4) cache that keeps the decode statistics of
+ * the bytes it reads (no reference counterpart: the reference kernel discards
+ * them).  The arguments up to codec, the query strides, the output layout
+ * [batch, q_max, heads, head_dim], the empty value -8.0, the GQA map, -1 blocks
+ * and the max_context_len clamp are kvecc_paged_attention_interp's; the
+ * workspace is kvecc_paged_attention_chunk_workspace at q_len = q_max; q_spans
+ * may be NULL (first 0, count q_max) and q_max 1 is the decode step.  codec must
+ * be KVECC_CODEC_H84, the caches must be under 4 GiB and stats must be non-NULL;
+ * anything else is KVECC_EINVAL with a message and launches nothing (callers
+ * fall back).  Golay, packed Golay and Hamming(7,4) caches are out of scope of
+ * this entry.
+ *
+ * Output.  interp == 0: kvecc_paged_attention_chunk_ragged's contract (single
+ * errors corrected, doubles keep their data), extended to q_max == 1 and NULL
+ * spans.  interp != 0: kvecc_paged_attention_interp's contract, word for word.
+ * Neither mode promises the bits of the uncounted kernels (fp32 summation
+ * order).
+ *
+ * Statistics.  Let n_b = min(context_lens[b], max_context_len,
+ * max_blocks*block_size).  One call adds to stats[0] / stats[1], for layer
+ * `layer`: for each sequence b that has at least one valid query token, each
+ * cache head, K and V, each stored byte of each position l < n_b whose
+ * block-table entry is >= 0, counted EXACTLY ONCE, its SINGLE_CORRECTED (type
+ * 1) / DOUBLE_DETECTED (type 2) classification; parity-only bytes (type 3) are
+ * not counted.  That is what kvecc_shim_read(ctx = n_b, stats) adds for that
+ * sequence alone.  Exactly once holds however the launch is cut: across the
+ * query heads of one cache head, the tokens of a chunk, the context splits, the
+ * one-pass-per-query-row form of the kernels, the interpolation's neighbour
+ * rows, padded rows and keys beyond a row's causal limit (a span that overruns
+ * q_max included: the positions past its last token's limit are counted and not
+ * attended).  Not counted: a sequence whose row is all padding (count <= 0 or
+ * first < 0 or first >= q_max), which is not read; positions >= n_b; other
+ * layers; -1 blocks.  stats is the library's sharded buffer (KVECC_STATS_SLOTS
+ * x KVECC_STATS_STRIDE, see the conventions above); totals accumulate across
+ * calls.  The launch path reads nothing on the host: the call replays in a
+ * captured graph.
+ *
+ * Kernels.  Counted siblings of the uncounted kernels, under their own names and
+ * over an argument block of their own: of the matrix-core kernels (fp16 queries,
+ * head_dim 32 / 64 / 128, both modes) and of the split kernels (every other dtype
+ * and head_dim <= 256, both modes).  Of each (sequence, cache head, context
+ * split) exactly one workgroup counts -- the first query-head group of the cache
+ * head, in the token tile (matrix cores) or query row (split kernels) of the
+ * sequence's last valid token, which walks the sequence's n_b rows -- on the
+ * words its lanes load anyway, in registers, with one reduction and at most two
+ * atomics per workgroup; every other workgroup runs the uncounted stream.  The
+ * interpolating kernels' neighbour rows are never counted. */
+KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                          int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                          const void *v_cache, const int32_t *block_table,
+                                          const int32_t *context_lens, const int32_t *q_spans,
+                                          const float *k_scales, const float *v_scales, void *out,
+                                          int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                          int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                          int64_t layer, int64_t block_size, int64_t max_blocks,
+                                          int64_t max_context_len, float sm_scale, int codec, int interp,
+                                          uint64_t *stats, float *workspace, int64_t workspace_floats,
+                                          void *stream);
+
 /* ---- Cache scrub --------------------------------------------------------------- */
 /* In-place patrol scrub of a resident paged cache (no reference counterpart:
  * the reference's cache lives for one forward, and every reader here corrects
@@ -735,6 +795,19 @@ KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batc
                                                int64_t layer, int64_t block_size, int64_t max_blocks,
                                                int64_t max_context_len, float sm_scale, int codec,
                                                int threads);
+/* host twin of kvecc_paged_attention_stats (q_spans may be NULL; stats a host buffer whose
+ * words 0 and 1 take the totals) */
+KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch_stride,
+                                              int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                              const void *k_cache, const void *v_cache,
+                                              const int32_t *block_table, const int32_t *context_lens,
+                                              const int32_t *q_spans, const float *k_scales,
+                                              const float *v_scales, void *out, int64_t batch,
+                                              int64_t q_max, int64_t heads, int64_t kv_heads,
+                                              int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                              int64_t layer, int64_t block_size, int64_t max_blocks,
+                                              int64_t max_context_len, float sm_scale, int codec, int interp,
+                                              uint64_t *stats, int threads);
 
 #ifdef __cplusplus
 }

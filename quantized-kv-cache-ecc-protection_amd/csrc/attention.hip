@@ -173,6 +173,19 @@ struct InterpArgs : RaggedArgs {};
 template <typename A>
 constexpr bool is_interp = std::is_same<A, InterpArgs>::value;
 
+// Counted calls (kvecc_paged_attention_stats, Hamming(8,4) only) run kernels of
+// their own names over argument blocks of their own: the ragged and the
+// interpolating block plus the library's sharded statistics buffer.  Every other
+// kernel keeps its block, its text and its registers.
+struct StatsArgs : RaggedArgs {
+  uint64_t *stats;  // KVECC_STATS_SLOTS x KVECC_STATS_STRIDE: [0] += SINGLE_CORRECTED, [1] += DOUBLE_DETECTED
+};
+struct StatsInterpArgs : InterpArgs {
+  uint64_t *stats;
+};
+template <typename A>
+constexpr bool is_stats = std::is_same<A, StatsArgs>::value || std::is_same<A, StatsInterpArgs>::value;
+
 // Byte caches without SECDED (KVECC_CODEC_H74, KVECC_CODEC_NONE: Hamming(8,4)'s
 // layout, uint8, one value per byte, rows of head_dim bytes) run one sibling
 // family of kernels, of their own names, over the Hamming(8,4) bodies: every
@@ -223,6 +236,15 @@ __device__ __forceinline__ uint32_t byte_table_nibble(const A &a, uint32_t b) {
 __device__ __forceinline__ uint32_t h84_double4(uint32_t w) {
   const uint32_t c = h_code4(w);  // syndrome in bits 0..2, parity error in bit 4 of each byte
   return ((c & 0x07070707u) + 0x07070707u) & ~(c >> 1) & 0x08080808u;
+}
+// The counted kernels' classification of four stored bytes, on the same first
+// look: type 1 (single corrected: syndrome != 0, overall parity odd) and type 2
+// (double detected); a parity-only byte (type 3) has syndrome 0 and is neither.
+__device__ __forceinline__ void h84_count4(uint32_t w, uint32_t &n_single, uint32_t &n_double) {
+  const uint32_t c = h_code4(w);
+  const uint32_t nz = ((c & 0x07070707u) + 0x07070707u) & 0x08080808u;
+  n_single += __builtin_popcount(nz & (c >> 1));
+  n_double += __builtin_popcount(nz & ~(c >> 1));
 }
 // ... and their slow path: four codewords decoded, the doubles replaced by
 // interp_word of the neighbours' decoded (not interpolated) values wl / wr, and
@@ -630,6 +652,28 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_interp_kernel(InterpA
 #include "attn_split_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the counted entry's kernels (kvecc_paged_attention_stats): the chunk form and the interpolating
+// form with the [statistics] islands, Hamming(8,4) over buffer-addressed caches only
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_stats_kernel(StatsArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_STATS 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_stats_interp_kernel(StatsInterpArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 2
+#define ATTN_BODY_STATS 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
 // the byte family's general path (KVECC_CODEC_H74 / KVECC_CODEC_NONE caches): the Hamming(8,4)
 // instantiations of the same body, the table by the argument block's selector
 template <typename T, int VEC, int W, bool BUF, int G = 1>
@@ -833,6 +877,26 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_interp_kernel(I
   using ChunkMap = ChunkMapT<RaggedArgs>;
 #include "attn_h84_mfma_interp_body.inc"
 }
+// the counted entry's (kvecc_paged_attention_stats): the ragged form and the interpolating
+// form with the [statistics] islands
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_stats_interp_kernel(StatsInterpArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_STATS 1
+#include "attn_h84_mfma_interp_body.inc"
+#undef ATTN_BODY_STATS
+}
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_stats_kernel(StatsArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_STATS 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
 // the byte family's: the decode, chunk and ragged kernels over the same body
 template <int D, int G>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_byte_mfma_kernel(ByteAttnArgs a) {
@@ -923,6 +987,11 @@ static int pow2_at_least(int64_t x) {
         KVECC_LAUNCH((paged_attn_split_byte_chunk_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
       else if constexpr (CODEC == KVECC_CODEC_H84)                                                              \
         KVECC_LAUNCH((paged_attn_split_byte_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
+    } else if constexpr (is_stats<A>) {                                                                         \
+      if constexpr (CODEC == KVECC_CODEC_H84 && BUF_ && std::is_same<A, StatsInterpArgs>::value)                \
+        KVECC_LAUNCH((paged_attn_split_stats_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);    \
+      else if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                      \
+        KVECC_LAUNCH((paged_attn_split_stats_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);           \
     } else if constexpr (is_interp<A>) {                                                                        \
       if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                           \
         KVECC_LAUNCH((paged_attn_split_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
@@ -1211,8 +1280,29 @@ static int launch_mfma_interp(const InterpArgs &a, int64_t batch, int64_t tiles,
   launch_combine<__half>(a, batch * a.q_len, st);
   return KVECC_OK;
 }
+// the counted entry's matrix-core kernels (uniform calls too: the spans are nullable)
+template <typename A>
+static int launch_mfma_stats(const A &a, int64_t batch, int64_t tiles, hipStream_t st) {
+  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
+#define KVECC_MFMA_STATS_LAUNCH(D_)                                                                  \
+  do {                                                                                               \
+    if constexpr (std::is_same<A, StatsInterpArgs>::value)                                           \
+      KVECC_LAUNCH((paged_attn_h84_mfma_stats_interp_kernel<D_>), grid, dim3(kBlock), 0, st, a);     \
+    else                                                                                             \
+      KVECC_LAUNCH((paged_attn_h84_mfma_stats_kernel<D_>), grid, dim3(kBlock), 0, st, a);            \
+  } while (0)
+  switch (a.d) {
+    case 32: KVECC_MFMA_STATS_LAUNCH(32); break;
+    case 64: KVECC_MFMA_STATS_LAUNCH(64); break;
+    default: KVECC_MFMA_STATS_LAUNCH(128); break;
+  }
+#undef KVECC_MFMA_STATS_LAUNCH
+  launch_combine<__half>(a, batch * a.q_len, st);
+  return KVECC_OK;
+}
 // ... and its general path: launch_codec_rows for the interpolating split kernels
-// (A InterpArgs) and for the byte family's (A ByteChunkArgs)
+// (A InterpArgs), for the byte family's (A ByteChunkArgs) and for the counted
+// ones (A StatsArgs / StatsInterpArgs)
 template <typename T, typename A>
 static int launch_h84_rows(A a, int64_t rows, int gq, hipStream_t st) {
   const int64_t wg_per_row = a.heads / gq;
@@ -1424,9 +1514,11 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
                                       int64_t num_blocks, int64_t num_layers, int64_t layer,
                                       int64_t block_size, int64_t max_blocks, int64_t max_context_len,
                                       float sm_scale, int codec, float *workspace, int64_t workspace_floats,
-                                      void *stream, bool interp = false) {
+                                      void *stream, bool interp = false, uint64_t *stats = nullptr) {
   if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
+  if (stats && codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
   if (interp && codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
   if (batch == 0 || q_len == 0 || heads == 0) return KVECC_OK;
@@ -1437,7 +1529,7 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
                      (long long)head_dim);
   // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
   // (a ragged call stays here: the decode entry knows no spans)
-  if (!interp && !q_spans && q_len == 1 && (heads == 1 || q_head_stride == head_dim) &&
+  if (!interp && !stats && !q_spans && q_len == 1 && (heads == 1 || q_head_stride == head_dim) &&
       (batch == 1 || q_batch_stride == heads * head_dim))
     return kvecc_paged_attention(query, q_dtype, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, batch, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size,
@@ -1517,10 +1609,13 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
   if (interp && !fits)
     return set_error(KVECC_EINVAL, "paged_attention_interp: caches of 4 GiB or more are not supported");
+  if (stats && !fits)
+    return set_error(KVECC_EINVAL, "paged_attention_stats: caches of 4 GiB or more are not supported");
   const int gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
   // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound);
   // an interpolating call takes its matrix-core kernels at q_len 1 too (one tile, the same bound: `finest`)
-  int gm = q_len > 1 || interp ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
+  // (a counted call takes its matrix-core kernels at every q_len too)
+  int gm = q_len > 1 || interp || stats ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
                                              head_dim, heads, kv_heads, fits)
                      : 0;
   int64_t wgs = 0;  // workgroups per split
@@ -1566,7 +1661,29 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   }
   hipStream_t st = as_stream(stream);
   int rc;
-  if (interp) {
+  if (stats) {  // the counted kernels' argument blocks
+    StatsArgs sa;
+    StatsInterpArgs si;
+    static_cast<RaggedArgs &>(sa) = a;
+    static_cast<RaggedArgs &>(si) = a;
+    sa.stats = si.stats = stats;
+    if (gm) {
+      rc = interp ? launch_mfma_stats(si, batch, tiles, st) : launch_mfma_stats(sa, batch, tiles, st);
+    } else {
+      switch (q_dtype) {
+        case KVECC_F32:
+          rc = interp ? launch_h84_rows<float>(si, vbatch, gq, st) : launch_h84_rows<float>(sa, vbatch, gq, st);
+          break;
+        case KVECC_F16:
+          rc = interp ? launch_h84_rows<__half>(si, vbatch, gq, st) : launch_h84_rows<__half>(sa, vbatch, gq, st);
+          break;
+        default:
+          rc = interp ? launch_h84_rows<__hip_bfloat16>(si, vbatch, gq, st)
+                      : launch_h84_rows<__hip_bfloat16>(sa, vbatch, gq, st);
+          break;
+      }
+    }
+  } else if (interp) {
     InterpArgs ia;  // the interpolating kernels' argument block
     static_cast<RaggedArgs &>(ia) = a;
     if (gm) {
@@ -1649,6 +1766,27 @@ KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_st
                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream, true);
+}
+
+KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                          int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                          const void *v_cache, const int32_t *block_table,
+                                          const int32_t *context_lens, const int32_t *q_spans,
+                                          const float *k_scales, const float *v_scales, void *out,
+                                          int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                          int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                          int64_t layer, int64_t block_size, int64_t max_blocks,
+                                          int64_t max_context_len, float sm_scale, int codec, int interp,
+                                          uint64_t *stats, float *workspace, int64_t workspace_floats,
+                                          void *stream) {
+  if (!stats) return set_error(KVECC_EINVAL, "paged_attention_stats: null stats");
+  if (codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
+  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream,
+                                    interp != 0, stats);
 }
 
 }  // extern "C"

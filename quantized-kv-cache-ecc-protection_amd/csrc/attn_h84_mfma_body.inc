@@ -5,6 +5,8 @@
 // attention.hip inside each kernel: the decode kernel's text is what it always
 // was, so its code is too (see ChunkArgs).
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
+// The counted kernel (paged_attn_h84_mfma_stats_kernel, `a` a StatsArgs, the ragged form) also
+// defines ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
   constexpr int KK = D / 32;  // QK MFMAs per 16-token tile
   constexpr int MT = D / 16;  // PV M-tiles; V bytes per lane per token
   constexpr int KB = D / 4;   // K bytes per lane per token
@@ -28,7 +30,19 @@
   }
   const int64_t b = cm.b, h0 = cm.h0;
   const int64_t hk = h0 / (a.heads / a.kv_heads);
+#ifdef ATTN_BODY_STATS  // [statistics] who counts (kvecc.h "Counted attention"): uniform per workgroup
+  // The tile that holds the sequence's last valid token, in the first column group of
+  // its cache head, counts: one workgroup per (sequence, cache head, split).  It walks
+  // the sequence's n_b rows -- the tile's largest key limit unless the span overruns
+  // q_max; the columns' own limits mask the scores either way ([score mask]).
+  const ChunkSpan csp(a, b);
+  const bool counts = csp.v1(a) > csp.v0() && cm.tile == (uint32_t)(csp.v1(a) - 1) / (16u >> a.cg_log2) &&
+                      h0 % (a.heads / a.kv_heads) == 0;
+  const int64_t ctx = counts ? min<int64_t>(a.ctx_lens[b], a.ctx_cap) : cm.ctx;
+  uint32_t n_single = 0, n_double = 0;
+#else
   const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns
+#endif
   const int64_t t0 = (int64_t)cm.split_idx * a.split;
 #else
   const int64_t hgroups = a.heads / G;
@@ -144,6 +158,25 @@
     const float *ks = cur.ks, *vs = cur.vs;
     auto &kw = cur.kw;
     auto &vw = cur.vw;
+#ifdef ATTN_BODY_STATS  // [statistics] every lane's K and V words are its own: each stored byte once
+    if (counts) {
+#pragma unroll
+      for (int tau = 0; tau < 2; ++tau) {
+        if (rows[i0 + 16 * tau + n] >= 0) {  // not a -1 block's / a past row's row 0
+#pragma unroll
+          for (int k = 0; k < KB / 4; ++k) h84_count4(kw[tau][k], n_single, n_double);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (rv[j] >= 0) {
+#pragma unroll
+          for (int k = 0; k < VW; ++k)  // (head_dim 32: two bytes per token, the rest of the dword as clean codewords)
+            h84_count4(MT < 4 ? vw[j][k] & ((1u << (8 * (MT & 3))) - 1u) : vw[j][k], n_single, n_double);
+        }
+      }
+    }
+#endif
     // ---- S^T = K . Q^T, two 16-token tiles
     f32x4 S[2];
 #pragma unroll
@@ -263,6 +296,12 @@
       ws_put(ws + 1, L);
     }
   }
+#ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
+  if (counts) {
+    const uint32_t cnt[2] = {n_single, n_double};
+    flush_stats_n<2>(a.stats, cnt);
+  }
+#endif
 #if !ATTN_BODY_CHUNK  // the counted combine: decode kernels only (chunk calls always launch the combine)
   if (a.ctr) combine_if_last<__half, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));
 #endif

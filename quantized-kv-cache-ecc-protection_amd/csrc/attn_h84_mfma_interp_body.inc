@@ -23,6 +23,10 @@
 //     so the corrected nibbles reach nib_pair_f16 through the same table as every
 //     other byte.  The neighbour loads of one K row (of four V rows) are issued
 //     together, one round trip; only the words that hold a double are rewritten.
+// The counted kernel (paged_attn_h84_mfma_stats_interp_kernel, `a` a StatsInterpArgs) defines
+// ATTN_BODY_STATS around its inclusion: the [statistics] islands, which count the words of
+// load_step -- every stored byte once -- and never the neighbour words of the slow path; without
+// it the preprocessed text is what it was.
   constexpr int KK = D / 32;  // QK MFMAs per 16-token tile
   constexpr int MT = D / 16;  // PV M-tiles; V bytes per lane per token
   constexpr int KB = D / 4;   // K bytes per lane per token
@@ -46,7 +50,16 @@
   }
   const int64_t b = cm.b, h0 = cm.h0;
   const int64_t hk = h0 / (a.heads / a.kv_heads);
+#ifdef ATTN_BODY_STATS  // [statistics] who counts: as in attn_h84_mfma_body.inc, uniform per workgroup
+  const ChunkSpan csp(a, b);
+  const bool counts = csp.v1(a) > csp.v0() && cm.tile == (uint32_t)(csp.v1(a) - 1) / (16u >> a.cg_log2) &&
+                      h0 % (a.heads / a.kv_heads) == 0;
+  // the sequence's n_b rows: the tile's largest key limit unless the span overruns q_max
+  const int64_t ctx = counts ? min<int64_t>(a.ctx_lens[b], a.ctx_cap) : cm.ctx;
+  uint32_t n_single = 0, n_double = 0;
+#else
   const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns
+#endif
   const int64_t t0 = (int64_t)cm.split_idx * a.split;
   const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
@@ -152,6 +165,24 @@
     const float *ks = cur.ks, *vs = cur.vs;
     auto &kw = cur.kw;
     auto &vw = cur.vw;
+#ifdef ATTN_BODY_STATS  // [statistics] the stored words, before any is rewritten; rows past n_b are -1
+    if (counts) {
+#pragma unroll
+      for (int tau = 0; tau < 2; ++tau) {
+        if (rows[kHalo + i0 + 16 * tau + n] >= 0) {
+#pragma unroll
+          for (int k = 0; k < KW; ++k) h84_count4(kw[tau][k], n_single, n_double);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (rv[j] >= 0) {
+#pragma unroll
+          for (int k = 0; k < VW; ++k) h84_count4(vw[j][k] & kVMask, n_single, n_double);
+        }
+      }
+    }
+#endif
     // ---- first look, then the slow path in the lanes that hold a double.  One K row, or four V
     // rows, at a time: their neighbour words are what the slow path keeps in registers, and
     // with all ten rows' at once the kernel took 225-256 VGPRs (2 waves per SIMD) for 140
@@ -304,3 +335,9 @@
       ws_put(ws + 1, L);
     }
   }
+#ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
+  if (counts) {
+    const uint32_t cnt[2] = {n_single, n_double};
+    flush_stats_n<2>(a.stats, cnt);
+  }
+#endif

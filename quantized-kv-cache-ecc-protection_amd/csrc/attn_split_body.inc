@@ -6,6 +6,8 @@
 // paged_attn_split_interp_kernel includes it at ATTN_BODY_CHUNK 2 (`a` an InterpArgs): the chunk
 // form plus the [interpolation] island; at 0 and 1 the preprocessed text is what it was.
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
+// The counted kernels (paged_attn_split_stats*_kernel, `a` a StatsArgs / StatsInterpArgs) also
+// define ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
   constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
   using C = Chunk<CODEC, VEC>;
   constexpr int E = C::E;
@@ -53,8 +55,21 @@
   const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);  // max_context_len and the table
 #endif
   const int64_t t0 = (int64_t)blockIdx.x * a.split;
+#ifdef ATTN_BODY_STATS  // [statistics] who counts (kvecc.h "Counted attention"): uniform per workgroup
+  // The row of the sequence's last valid token, in the first query-head group of
+  // its cache head, counts: one workgroup per (sequence, cache head, split).  It
+  // walks the sequence's n_b rows -- its own key limit unless the span overruns
+  // q_max, where the rows past the limit are counted and masked (ntok_att).
+  const bool counts = row_ok && (int64_t)tq + 1 == sp.v1(a) && h0 % (a.heads / a.kv_heads) == 0;
+  const int64_t walk = counts ? min<int64_t>(a.ctx_lens[bt], a.ctx_cap) : ctx;
+  const int64_t t1 = min<int64_t>(t0 + a.split, walk);
+  const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
+  const int ntok_att = (int)max<int64_t>(min<int64_t>(ctx - t0, ntok), 0);
+  uint32_t n_single = 0, n_double = 0;
+#else
   const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
+#endif
   const bool live = c < (a.g + VEC - 1) / VEC;  // lanes past the row idle
   const int cs = live ? c : 0;
   const int64_t ws_stride = a.nsplit * (a.d + 2);  // per query head
@@ -214,6 +229,21 @@
       ok[u] = pok[u];
     }
     if (kPrefetch && i0 + TP * U < ntok) load_rows(i0 + TP * U);
+#ifdef ATTN_BODY_STATS  // [statistics] the stored bytes of the lane's words, before any interpolation
+    if (counts) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (live && ok[u]) {  // not the idle lanes' copy of lane 0, nor a -1 block's / a past row's row 0
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            h84_count4(kc[u].w[k], n_single, n_double);
+            h84_count4(vc[u].w[k], n_single, n_double);
+          }
+        }
+        ok[u] = ok[u] && i0 + u * TP < ntok_att;  // rows past the row's own key limit: counted, not attended
+      }
+    }
+#endif
 #if ATTN_BODY_CHUNK == 2  // [interpolation] paged_attn_split_interp_kernel only (kvecc.h "Interpolated attention")
     // First look: h84_double4 of the lane's words.  A lane whose K or V words of
     // a row hold a type-2 byte re-loads the same words of the rows at positions
@@ -354,4 +384,10 @@
       ws_put(ws + 1, L);
     }
   }
+#ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
+  if (counts) {
+    const uint32_t cnt[2] = {n_single, n_double};
+    flush_stats_n<2>(a.stats, cnt);
+  }
+#endif
   if (a.ctr) combine_if_last<T, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));

@@ -636,9 +636,9 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
-                               interp=False):
+                               interp=False, stats=None):
     """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
-    from .ops import _check_attention_chunk_args, _check_interp_codec, _check_q_spans
+    from .ops import _check_attention_chunk_args, _check_interp_codec, _check_q_spans, _check_stats_codec
     _check_cpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
@@ -647,6 +647,23 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     batch, q_len, heads, head_dim = query.shape
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
+    if stats is not None:  # kvecc_cpu_paged_attention_stats: the totals go to words 0 and 1
+        _check_stats_codec(codec)
+        if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
+                or stats.numel() < 2 or stats.device.type != "cpu"):
+            raise ValueError("stats must be a contiguous int64 host tensor of >= 2 elements (cpu_ops.new_stats), got "
+                             f"{getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
+                             f"on {getattr(stats, 'device', None)}")
+        sp = _ptr(stats)
+        if q_spans is not None:
+            _check_q_spans(q_spans, batch, query.device)
+        _lib.call("kvecc_cpu_paged_attention_stats", _ptr(query), query.stride(0), query.stride(1),
+                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+                  int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), sp,
+                  NUM_THREADS)
+        return out
     if interp:
         if q_spans is not None:
             _check_q_spans(q_spans, batch, query.device)

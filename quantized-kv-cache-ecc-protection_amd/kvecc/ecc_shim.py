@@ -135,6 +135,18 @@ class ECCShimConfig:
     on NO decode statistics are kept (``chunk_attention`` alone leaves these
     codecs on the read + SDPA path).  For hamming74, scrub_ecc_cache still
     supplies the counts; int4 has nothing to count.
+    ``stats_attention`` (append mode, hamming84 with or without
+    use_interpolation, opt-in) sends every forward of ``_append_attend`` --
+    single-token steps, the prefill, chunks, held spans -- through the counted
+    paged attention (kvecc_paged_attention_stats) when head_dim <= 256: the
+    kernels count the SINGLE_CORRECTED / DOUBLE_DETECTED bytes they read into the
+    shim's statistics, exactly what ``decode_stats=True`` counts through the
+    read + SDPA path, and interpolate doubles inline iff use_interpolation.  It
+    takes precedence over decode_stats, chunk_attention and interp_attention;
+    head_dim > 256 falls back to the read + SDPA path.  One deliberate
+    difference: with held spans, a sequence that has no valid
+    token in the forward is not read and so not counted, where the rectangular
+    read counts it.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -145,7 +157,8 @@ class ECCShimConfig:
     def __init__(self, codec="hamming84", ber=0.0, block_size=16, num_blocks=256,
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
-                 decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False):
+                 decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False,
+                 stats_attention=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -183,6 +196,10 @@ class ECCShimConfig:
                              f"(hamming84 and golay take the kernels by default), not codec={codec!r}, "
                              f"cache_mode={cache_mode!r}")
         self.kernel_attention = bool(kernel_attention)
+        if stats_attention and (cache_mode != "append" or codec != "hamming84"):
+            raise ValueError("stats_attention=True needs cache_mode='append' and codec='hamming84', "
+                             f"not codec={codec!r}, cache_mode={cache_mode!r}")
+        self.stats_attention = bool(stats_attention)
 
 
 class SimpleBlockManager:
@@ -664,6 +681,26 @@ class ECCBackend:
         interp = cfg.use_interpolation and cfg.codec == "hamming84"
         # hamming74 / int4 take the kernels only under kernel_attention (their codec is checked there)
         kernel_codec = cfg.codec in ("hamming84", "golay") or cfg.kernel_attention
+        if cfg.stats_attention and d <= 256:
+            # every q_len on the counted kernels: q read in place as [batch, q_len,
+            # heads, d], the decode statistics of the bytes read added to the shim's
+            # buffer, doubles interpolated inline iff use_interpolation
+            sp = None
+            if self._spans is not None:
+                self._check_spans(b, q_len)
+                sp = self._span_buf[:b]
+            qt = q.transpose(1, 2)
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention_stats(
+                    qt, mgr.k_cache, mgr.v_cache, table, dev_lens, sp, mgr.k_scales, mgr.v_scales, self._stats,
+                    layer_idx, mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, interp, ctx)
+                return out.transpose(1, 2)
+            out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+            self.codec_backend.paged_attention_chunk_into(
+                qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx, q_spans=sp,
+                interp=interp, stats=self._stats)
+            return out.transpose(1, 2)
         if q_len == 1 and kernel_codec and not interp and not cfg.decode_stats and d <= 256:
             # decode step: paged attention with inline decode over the ragged
             # tables; no statistics, as on the reference's seq_len == 1 path

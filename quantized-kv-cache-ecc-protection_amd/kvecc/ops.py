@@ -1233,9 +1233,14 @@ def _check_interp_codec(codec):
         raise ValueError(f"interp needs hamming84, got codec {codec!r}")
 
 
+def _check_stats_codec(codec):
+    if codec != "hamming84":
+        raise ValueError(f"stats needs hamming84 (the counted attention kernels), got codec {codec!r}")
+
+
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
-                               interp=False):
+                               interp=False, stats=None):
     """kvecc_paged_attention_chunk: q_len query tokens per sequence, causal (include/kvecc.h).
 
     query [B, q_len, H, D] with any strides and a unit innermost one (the
@@ -1253,12 +1258,23 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     interp=True (hamming84 only; kvecc_paged_attention_interp): detected double
     errors of the stored keys and values are interpolated from the neighbouring
     tokens of their own sequence, as shim_read(interp=True) reads them; with or
-    without q_spans, q_len 1 included."""
+    without q_spans, q_len 1 included.
+
+    stats (hamming84 only; an ops.new_stats buffer on the query's device;
+    kvecc_paged_attention_stats): the counted kernels, which add the
+    SINGLE_CORRECTED / DOUBLE_DETECTED classification of every stored K and V byte
+    of each sequence that has a valid token to stats[0] / stats[1], exactly once,
+    as shim_read(ctx = n_b, stats) counts them; with or without interp and
+    q_spans, q_len 1 included."""
     _check_gpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
     if interp:
         _check_interp_codec(codec)
+    sp = None
+    if stats is not None:
+        _check_stats_codec(codec)
+        sp = _sptr(stats, query.device)
     batch, q_len, heads, head_dim = query.shape
     if q_spans is not None:
         _check_q_spans(q_spans, batch, query.device)
@@ -1267,6 +1283,14 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
     ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
     ws = _attn_workspace(query.device, ws_n)
+    if sp is not None:
+        _lib.call("kvecc_paged_attention_stats", _ptr(query), query.stride(0), query.stride(1),
+                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+                  mcl, float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), sp, _ptr(ws), ws.numel(),
+                  _stream(query.device))
+        return out
     if interp:
         _lib.call("kvecc_paged_attention_interp", _ptr(query), query.stride(0), query.stride(1),
                   query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
@@ -1291,10 +1315,11 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
 
 def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                           layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0,
-                          q_spans=None, interp=False):
+                          q_spans=None, interp=False, stats=None):
     """paged_attention_chunk_into with a fresh [B, q_len, H, D] output; on the
     GPU or, for host tensors, through the host twin.  q_spans: a ragged call;
-    interp: double errors interpolated (hamming84)."""
+    interp: double errors interpolated (hamming84); stats: the counted kernels
+    (hamming84), decode statistics added to the buffer."""
     if sm_scale is None:
         sm_scale = 1.0 / math.sqrt(query.shape[-1])
     out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
@@ -1303,10 +1328,11 @@ def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_
         return cpu_ops.paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
                                                   v_scales, out, layer_idx, block_size, sm_scale, codec,
                                                   max_context_len=max_context_len, q_spans=q_spans,
-                                                  interp=interp)
+                                                  interp=interp, stats=stats)
     return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                       out, layer_idx, block_size, sm_scale, codec,
-                                      max_context_len=max_context_len, q_spans=q_spans, interp=interp)
+                                      max_context_len=max_context_len, q_spans=q_spans, interp=interp,
+                                      stats=stats)
 
 
 def _conform(t, dtype):

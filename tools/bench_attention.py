@@ -32,6 +32,13 @@ hamming74 and hamming84 on clean encoded caches of the same nibbles, hamming74 a
 injected at BER 1e-3, and shim_read_batch + repeat_interleave + masked SDPA over the int4 and
 hamming74 caches, the path ECCShimConfig(kernel_attention=True) replaces.
 
+--stats times the counted entry (kvecc_paged_attention_stats, Hamming(8,4)) in one process at
+--kv-heads and --heads / 4 cache heads, q_len 1 and 16, on a clean encoded cache and on one injected
+at BER 1e-3, one JSON line per case, every pass visiting the cases in turn: the counted entry with
+interp 0 and 1, the uncounted plain (decode / chunk) and interpolating entries on the same cache,
+and shim_read_batch(stats=...) + repeat_interleave + masked SDPA, the path
+ECCShimConfig(stats_attention=True) replaces (with and without interpolation).
+
 --pkg DIR imports kvecc from DIR instead of this tree (the same measurement on
 another build, e.g. the parent commit's, in the same session).
 """
@@ -88,6 +95,8 @@ def main():
     ap.add_argument("--interp", action="store_true", help="the interpolating entry against (a), (b), (c) above")
     ap.add_argument("--bytes", action="store_true",
                     help="the byte family (int4, hamming74) beside hamming84, alternated in one process")
+    ap.add_argument("--stats", action="store_true",
+                    help="the counted entry beside the uncounted kernels and the counting read + SDPA")
     ap.add_argument("--pkg", default=None, help="directory to import kvecc from (default: this tree)")
     args = ap.parse_args()
     if args.pkg:
@@ -98,6 +107,8 @@ def main():
         return bench_interp(args, ops, dev)
     if args.bytes:
         return bench_bytes(args, ops, dev)
+    if args.stats:
+        return bench_stats(args, ops, dev)
     g = torch.Generator(device=dev).manual_seed(0)
     nb = (args.ctx + args.bs - 1) // args.bs
     blocks = args.batch * nb
@@ -431,6 +442,104 @@ def bench_bytes(args, ops, dev):
                               "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
                               "block_size": args.bs, **res}), flush=True)
         del caches, x
+
+
+def bench_stats(args, ops, dev):
+    import statistics
+    import time
+
+    import torch.nn.functional as F
+    from kvecc.memory_layout import kv_cache_pair
+    if args.codec != "hamming84":
+        raise SystemExit("--stats needs --codec hamming84")
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    sm = 1 / math.sqrt(args.d)
+
+    def timed_alternating(cases):
+        """Every case warmed up, then --passes rounds that visit the cases in turn."""
+        for fn in cases.values():
+            t0 = time.perf_counter()
+            while True:
+                for _ in range(args.warmup):
+                    fn()
+                torch.cuda.synchronize()
+                if time.perf_counter() - t0 >= args.warmup_s:
+                    break
+        passes = {name: [] for name in cases}
+        for _ in range(args.passes):
+            for name, fn in cases.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                passes[name].append(e0.elapsed_time(e1) / args.iters * 1e3)
+        return {name: {"us_per_call": round(statistics.median(p), 2), "pass_us": [round(x, 2) for x in p],
+                       "spread_us": round(max(p) - min(p), 2)} for name, p in passes.items()}
+
+    for kvh in (args.kv_heads, max(1, args.heads // 4)):
+        x = torch.randint(0, 16, (2, blocks, 1, kvh, args.bs, args.d), device=dev, generator=g, dtype=torch.uint8)
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        groups = args.heads // kvh
+        for ber in (0.0, 1e-3):
+            kc, vc = kv_cache_pair((blocks, 1, kvh, args.bs * args.d), torch.uint8, dev)
+            for side, dst in enumerate((kc, vc)):
+                cw = ops.hamming84_encode(x[side].reshape(-1))
+                if ber > 0:
+                    ops.inject_into(cw, cw, ber, 8, seed=42 + side)
+                dst.view(-1).copy_(cw)
+            for n in (1, 16):
+                qc = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half()
+                qt = qc.transpose(1, 2)
+                q1 = qc[:, :, 0].contiguous()
+                outc = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+                out1 = torch.empty_like(q1)
+                stats = ops.new_stats(dev)
+
+                def counted(interp):
+                    return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm,
+                                                                  "hamming84", args.ctx, interp=interp, stats=stats)
+
+                def uncounted(interp):
+                    if n == 1:
+                        return lambda: ops.paged_attention_into(q1, kc, vc, table, lens, ks, vs, out1, 0, args.bs, sm,
+                                                                "hamming84", args.ctx, interp=interp)
+                    return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs,
+                                                                  sm, "hamming84", args.ctx, interp=interp)
+
+                def read_sdpa(interp):
+                    def fn():
+                        k_t, v_t = ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, "hamming84",
+                                                       qc.dtype, stats=stats, interp=interp)
+                        if groups > 1:
+                            k_t = k_t.repeat_interleave(groups, dim=1)
+                            v_t = v_t.repeat_interleave(groups, dim=1)
+                        qpos = (lens - n).view(-1, 1, 1) + torch.arange(n, device=dev).view(1, n, 1)
+                        mask = torch.arange(args.ctx, device=dev).view(1, 1, args.ctx) <= qpos
+                        return F.scaled_dot_product_attention(qc, k_t, v_t, attn_mask=mask.unsqueeze(1))
+                    return fn
+
+                # one counted call's totals against one counting read's: the same bytes, counted alike
+                ref = ops.new_stats(dev)
+                ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, "hamming84", qc.dtype, stats=ref)
+                counted(False)()
+                totals = ops.read_stats(stats)
+                assert totals == ops.read_stats(ref), (totals, ops.read_stats(ref))
+                res = timed_alternating({"counted_plain": counted(False), "counted_interp": counted(True),
+                                         "uncounted_plain": uncounted(False), "uncounted_interp": uncounted(True)})
+                res.update(timed_alternating({"read_stats_sdpa": read_sdpa(False),
+                                              "read_stats_interp_sdpa": read_sdpa(True)}))
+                print(json.dumps({"kernel": "paged_attention_stats", "batch": args.batch, "q_len": n,
+                                  "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
+                                  "block_size": args.bs, "ber": ber, "counts_per_call": totals, **res}), flush=True)
+            del kc, vc
+        del x
 
 
 if __name__ == "__main__":
