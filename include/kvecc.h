@@ -608,6 +608,56 @@ KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_str
                                           uint64_t *stats, float *workspace, int64_t workspace_floats,
                                           void *stream);
 
+/* The same over a Golay(24,12) cache (no reference counterpart).  The arguments
+ * are kvecc_paged_attention_stats's without interp (the reference interpolates
+ * no Golay word).  codec must be KVECC_CODEC_GOLAY or KVECC_CODEC_GOLAY_PACKED
+ * and stats non-NULL; anything else is KVECC_EINVAL with a message (naming golay
+ * for a wrong codec, stats for a NULL buffer) and launches nothing.
+ * kvecc_paged_attention_stats itself keeps rejecting every codec but
+ * Hamming(8,4).  head_dim (<= 256), the query dtypes and the cache layouts are
+ * kvecc_paged_attention_chunk_ragged's for Golay, except that the counted
+ * kernels address the caches through buffer descriptors only: caches (or scale
+ * arrays) of 4 GiB or more are KVECC_EINVAL with a message.
+ *
+ * Output.  kvecc_paged_attention_chunk_ragged's contract for Golay --
+ * uncorrectable words keep their data, the empty value is 0, padding rows are
+ * never read, its GQA map, -1 blocks and max_context_len clamp -- extended to
+ * q_max == 1 and NULL spans; not the uncounted kernels' bits (fp32 summation
+ * order, and the launcher may pick another kernel family for the same shape).
+ *
+ * Statistics.  With n_b as above, one call adds for layer `layer`, for each
+ * sequence with at least one valid query token, each cache head, K and V, each
+ * position l < n_b whose block-table entry is >= 0 and each of the row's g =
+ * ceil(head_dim / 3) codewords, EXACTLY ONCE: stats[0] += the decoder's count
+ * when it is 0..3 (bits corrected, parity bits included), stats[1] += 1 when it
+ * is 4 (uncorrectable) -- bit for bit what kvecc_shim_read(ctx = n_b, stats)
+ * adds for that sequence alone.  Exactly once holds however the launch is cut,
+ * as above.  Never counted: bits 24..31 of an int32 word, the pad bytes of a
+ * packed row, the codewords past g - 1 that a lane's wider load brings in (the
+ * next row's, or past the buffer), the row that a -1 block's lanes read in its
+ * place, positions >= n_b, other layers, all-padding sequences.  The buffer,
+ * the accumulation across calls and graph replay are as above.
+ *
+ * Kernels.  Counted siblings of the ragged Golay kernels, under their own names:
+ * two matrix-core kernels (fp16 queries, head_dim 128; int32 and packed), which
+ * read the count from byte 3 of the correction entry their decode fetches
+ * anyway, and the split kernels (every other dtype, group and head_dim), which
+ * read it from bits 16-23 of theirs.  A decode step (q_max 1) without GQA takes
+ * the split kernels.  The counting workgroup is chosen as above; the other
+ * workgroups of the matrix-core kernels carry the count byte through their
+ * decode (one more instruction per codeword) and add nothing. */
+KVECC_API int kvecc_paged_attention_golay_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                                int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                                const void *v_cache, const int32_t *block_table,
+                                                const int32_t *context_lens, const int32_t *q_spans,
+                                                const float *k_scales, const float *v_scales, void *out,
+                                                int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                int64_t max_context_len, float sm_scale, int codec,
+                                                uint64_t *stats, float *workspace, int64_t workspace_floats,
+                                                void *stream);
+
 /* ---- Cache scrub --------------------------------------------------------------- */
 /* In-place patrol scrub of a resident paged cache (no reference counterpart:
  * the reference's cache lives for one forward, and every reader here corrects
@@ -808,6 +858,18 @@ KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch
                                               int64_t layer, int64_t block_size, int64_t max_blocks,
                                               int64_t max_context_len, float sm_scale, int codec, int interp,
                                               uint64_t *stats, int threads);
+/* host twin of kvecc_paged_attention_golay_stats (as above) */
+KVECC_API int kvecc_cpu_paged_attention_golay_stats(const void *query, int64_t q_batch_stride,
+                                                    int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                                    const void *k_cache, const void *v_cache,
+                                                    const int32_t *block_table, const int32_t *context_lens,
+                                                    const int32_t *q_spans, const float *k_scales,
+                                                    const float *v_scales, void *out, int64_t batch,
+                                                    int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                    int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                    int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                    int64_t max_context_len, float sm_scale, int codec,
+                                                    uint64_t *stats, int threads);
 
 #ifdef __cplusplus
 }

@@ -176,9 +176,13 @@ constexpr bool is_interp = std::is_same<A, InterpArgs>::value;
 // Counted calls (kvecc_paged_attention_stats, Hamming(8,4) only) run kernels of
 // their own names over argument blocks of their own: the ragged and the
 // interpolating block plus the library's sharded statistics buffer.  Every other
-// kernel keeps its block, its text and its registers.
+// kernel keeps its block, its text and its registers.  The Golay counted kernels
+// (kvecc_paged_attention_golay_stats) are further kernels of their own names over
+// StatsArgs: the uncounted Golay kernels never see it.
 struct StatsArgs : RaggedArgs {
-  uint64_t *stats;  // KVECC_STATS_SLOTS x KVECC_STATS_STRIDE: [0] += SINGLE_CORRECTED, [1] += DOUBLE_DETECTED
+  // KVECC_STATS_SLOTS x KVECC_STATS_STRIDE: [0] += SINGLE_CORRECTED, [1] += DOUBLE_DETECTED
+  // (Golay: [0] += bits corrected, [1] += uncorrectable words)
+  uint64_t *stats;
 };
 struct StatsInterpArgs : InterpArgs {
   uint64_t *stats;
@@ -417,6 +421,18 @@ struct Chunk {
         asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(v[3 * k + 2]) : "v"(sp));  // 16 n
       }
     }
+  }
+  // The counted Golay kernels' look at word k (the [statistics] island of
+  // attn_split_body.inc): the count field of its correction entry, bits 16-23
+  // of golay_attn_x_table_dev's second half -- (bits corrected & 3) |
+  // uncorrectable << 6, which decode() masks off -- through decode()'s two
+  // lookups.  Bits 0-1 and 26-31 of w (an int32 word's bits 24-31, a packed
+  // neighbour's bytes) take no part, as in decode().
+  __device__ __forceinline__ uint32_t count(const uint32_t *gtab, int k) const {
+    const char *tb = reinterpret_cast<const char *>(gtab);
+    const uint32_t p = *reinterpret_cast<const uint32_t *>(tb + (w[k] & 0x3FFCu));
+    const uint32_t off = __builtin_amdgcn_bitop3_b32(w[k], p, 0x03FFC000u, 0x28) >> 12;
+    return (*reinterpret_cast<const uint32_t *>(tb + 16384 + off) >> 16) & 0xFFu;
   }
 };
 
@@ -669,6 +685,19 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_stats_interp_kernel(S
   constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
   constexpr bool BUF = true;
 #define ATTN_BODY_CHUNK 2
+#define ATTN_BODY_STATS 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
+// the Golay counted entry's kernels (kvecc_paged_attention_golay_stats): the chunk form with the
+// [statistics] islands, int32 and packed caches, buffer-addressed only
+template <typename T, int CODEC, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_golay_stats_kernel(StatsArgs a) {
+  static_assert(is_golay(CODEC), "the Golay counted kernels");
+  constexpr int UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 1
 #define ATTN_BODY_STATS 1
 #include "attn_split_body.inc"
 #undef ATTN_BODY_STATS
@@ -963,6 +992,18 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_ragged_kernel
 #include "attn_golay_mfma_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the counted entry's (kvecc_paged_attention_golay_stats): the ragged form with the [statistics]
+// islands, at every q_max
+template <bool PACKED>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_stats_kernel(StatsArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_STATS 1
+#include "attn_golay_mfma_body.inc"
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
 
 template <typename T>
 static void launch_combine(const AttnArgs &a, int64_t batch, hipStream_t st) {
@@ -992,7 +1033,10 @@ static int pow2_at_least(int64_t x) {
         KVECC_LAUNCH((paged_attn_split_stats_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);    \
       else if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                      \
         KVECC_LAUNCH((paged_attn_split_stats_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);           \
-    } else if constexpr (is_interp<A>) {                                                                        \
+      else if constexpr (is_golay(CODEC) && BUF_ && std::is_same<A, StatsArgs>::value)                          \
+        KVECC_LAUNCH((paged_attn_split_golay_stats_kernel<T, CODEC, VEC_, WW, G_>), grid, dim3(kBlock), 0, st,  \
+                     a);                                                                                        \
+    } else if constexpr (is_interp<A>) {                                                                       \
       if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                           \
         KVECC_LAUNCH((paged_attn_split_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
     } else if constexpr (is_chunk<A>)                                                                           \
@@ -1300,7 +1344,36 @@ static int launch_mfma_stats(const A &a, int64_t batch, int64_t tiles, hipStream
   launch_combine<__half>(a, batch * a.q_len, st);
   return KVECC_OK;
 }
-// ... and its general path: launch_codec_rows for the interpolating split kernels
+// the Golay counted entry's matrix-core kernels and its general path (launch_codec_rows over a
+// StatsArgs: the virtual batch in slices that fit grid.y, then one combine)
+static int launch_golay_mfma_stats(int codec, const StatsArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
+  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
+  if (codec == KVECC_CODEC_GOLAY_PACKED)
+    KVECC_LAUNCH((paged_attn_golay_mfma_stats_kernel<true>), grid, dim3(kBlock), 0, st, a);
+  else
+    KVECC_LAUNCH((paged_attn_golay_mfma_stats_kernel<false>), grid, dim3(kBlock), 0, st, a);
+  launch_combine<__half>(a, batch * a.q_len, st);
+  return KVECC_OK;
+}
+template <typename T>
+static int launch_golay_stats_rows(int codec, StatsArgs a, int64_t rows, int gq, hipStream_t st) {
+  const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
+  auto launch = [&](int64_t n, bool combine) {
+    return packed ? launch_attn<T, KVECC_CODEC_GOLAY_PACKED>(a, n, gq, st, combine)
+                  : launch_attn<T, KVECC_CODEC_GOLAY>(a, n, gq, st, combine);
+  };
+  const int64_t wg_per_row = a.heads / gq;
+  if (rows * wg_per_row <= kMaxGridY) return launch(rows, true);
+  const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
+  for (int64_t vb = 0; vb < rows; vb += per) {
+    a.vb0 = (uint32_t)vb;
+    const int rc = launch(std::min(per, rows - vb), false);
+    if (rc != KVECC_OK) return rc;
+  }
+  launch_combine<T>(a, rows, st);
+  return KVECC_OK;
+}
+// The Hamming(8,4) layout's general path: launch_codec_rows for the interpolating split kernels
 // (A InterpArgs), for the byte family's (A ByteChunkArgs) and for the counted
 // ones (A StatsArgs / StatsInterpArgs)
 template <typename T, typename A>
@@ -1514,10 +1587,12 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
                                       int64_t num_blocks, int64_t num_layers, int64_t layer,
                                       int64_t block_size, int64_t max_blocks, int64_t max_context_len,
                                       float sm_scale, int codec, float *workspace, int64_t workspace_floats,
-                                      void *stream, bool interp = false, uint64_t *stats = nullptr) {
+                                      void *stream, bool interp = false, uint64_t *stats = nullptr,
+                                      bool golay_stats = false) {
   if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
-  if (stats && codec != KVECC_CODEC_H84)
+  // golay_stats: kvecc_paged_attention_golay_stats, which has checked its codec and its buffer
+  if (stats && !golay_stats && codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
   if (interp && codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
@@ -1610,7 +1685,8 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   if (interp && !fits)
     return set_error(KVECC_EINVAL, "paged_attention_interp: caches of 4 GiB or more are not supported");
   if (stats && !fits)
-    return set_error(KVECC_EINVAL, "paged_attention_stats: caches of 4 GiB or more are not supported");
+    return set_error(KVECC_EINVAL, "%s: caches of 4 GiB or more are not supported",
+                     golay_stats ? "paged_attention_golay_stats" : "paged_attention_stats");
   const int gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
   // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound);
   // an interpolating call takes its matrix-core kernels at q_len 1 too (one tile, the same bound: `finest`)
@@ -1618,6 +1694,8 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   int gm = q_len > 1 || interp || stats ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
                                              head_dim, heads, kv_heads, fits)
                      : 0;
+  // (a counted Golay decode step without GQA stays on the split kernels, as the decode entry's does: attn_mfma_heads)
+  if (golay_stats && q_len == 1 && heads == kv_heads) gm = 0;
   int64_t wgs = 0;  // workgroups per split
   if (gm) {
     for (a.cg_log2 = 0; (1 << a.cg_log2) < gm; ++a.cg_log2) {}
@@ -1661,7 +1739,20 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
   }
   hipStream_t st = as_stream(stream);
   int rc;
-  if (stats) {  // the counted kernels' argument blocks
+  if (golay_stats) {  // the Golay counted kernels: StatsArgs too
+    StatsArgs sa;
+    static_cast<RaggedArgs &>(sa) = a;
+    sa.stats = stats;
+    if (gm) {
+      rc = launch_golay_mfma_stats(codec, sa, batch, tiles, st);
+    } else {
+      switch (q_dtype) {
+        case KVECC_F32: rc = launch_golay_stats_rows<float>(codec, sa, vbatch, gq, st); break;
+        case KVECC_F16: rc = launch_golay_stats_rows<__half>(codec, sa, vbatch, gq, st); break;
+        default: rc = launch_golay_stats_rows<__hip_bfloat16>(codec, sa, vbatch, gq, st); break;
+      }
+    }
+  } else if (stats) {  // the counted kernels' argument blocks
     StatsArgs sa;
     StatsInterpArgs si;
     static_cast<RaggedArgs &>(sa) = a;
@@ -1787,6 +1878,28 @@ KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_str
                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream,
                                     interp != 0, stats);
+}
+
+KVECC_API int kvecc_paged_attention_golay_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                                int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                                const void *v_cache, const int32_t *block_table,
+                                                const int32_t *context_lens, const int32_t *q_spans,
+                                                const float *k_scales, const float *v_scales, void *out,
+                                                int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                int64_t max_context_len, float sm_scale, int codec,
+                                                uint64_t *stats, float *workspace, int64_t workspace_floats,
+                                                void *stream) {
+  if (!stats) return set_error(KVECC_EINVAL, "paged_attention_golay_stats: null stats");
+  if (codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL, "paged_attention_golay_stats: codec %d (these counted kernels need golay or golay_packed)",
+                     codec);
+  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream, false,
+                                    stats, true);
 }
 
 }  // extern "C"

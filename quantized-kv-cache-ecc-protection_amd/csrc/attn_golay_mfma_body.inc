@@ -5,6 +5,8 @@
 // attention.hip inside each kernel: the decode kernel's text is what it always
 // was, so its code is too (see ChunkArgs).
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
+// The counted kernel (paged_attn_golay_mfma_stats_kernel, `a` a StatsArgs, the ragged form) also
+// defines ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
   constexpr int D = 128, GC = 43;          // head_dim, codewords per row
   constexpr int KC = PACKED ? 12 : 11;     // K codewords per lane group
   constexpr int KD = 3 * KC, KK = 5;       // its values; QK MFMAs per 16 tokens
@@ -30,7 +32,18 @@
   }
   const int64_t b = cm.b, h0 = cm.h0;
   const int64_t hk = h0 / (a.heads / a.kv_heads);
+#ifdef ATTN_BODY_STATS  // [statistics] who counts (kvecc.h "Counted attention"): uniform per workgroup
+  // As in attn_h84_mfma_body.inc: the tile that holds the sequence's last valid token, in
+  // the first column group of its cache head -- one workgroup per (sequence, cache head,
+  // split).  It walks the sequence's n_b rows; the columns' own limits mask the scores.
+  const ChunkSpan csp(a, b);
+  const bool counts = csp.v1(a) > csp.v0() && cm.tile == (uint32_t)(csp.v1(a) - 1) / (16u >> a.cg_log2) &&
+                      h0 % (a.heads / a.kv_heads) == 0;
+  const int64_t ctx = counts ? min<int64_t>(a.ctx_lens[b], a.ctx_cap) : cm.ctx;
+  uint32_t n_bits = 0, n_unc = 0;  // bits corrected (counts 1..3), uncorrectable words (count 4)
+#else
   const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns
+#endif
   const int64_t t0 = (int64_t)cm.split_idx * a.split;
 #else
   const int64_t hgroups = a.heads / G;
@@ -109,12 +122,27 @@
   // their data.  (The split kernels' table, parity at the codeword's parity
   // bits and the nibbles in bytes 0, 1, 3, measured 1 % slower here:
   // profiles/r04/attn/xtab_ab.log.)
+#ifdef ATTN_BODY_STATS  // [statistics] the decoded word keeps the correction entry's byte 3: (bits corrected & 3) |
+  // uncorrectable << 6 (runtime.hip, ensure_tables), one v_and_or more per codeword; `pair` reads bytes 0..2 only
+  auto sp_of = [&](uint32_t c) -> uint32_t {
+    const uint32_t p = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(gt) + ((c << 2) & 0x3FFCu));
+    const uint32_t off = ((c >> 10) ^ (p >> 18)) & 0x3FFCu;
+    const uint32_t e = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(gt + 4096) + off);
+    return (e & 0xFF000000u) | __builtin_amdgcn_bitop3_b32(p, e, 0x000F0F0Fu, 0x28);
+  };
+  // the count fields of up to 21 codewords summed (3 * 21 < 64), folded into the lane's counters
+  auto fold = [&](uint32_t f) {
+    n_bits += f & 0x3Fu;
+    n_unc += f >> 6;
+  };
+#else
   auto sp_of = [&](uint32_t c) -> uint32_t {
     const uint32_t p = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(gt) + ((c << 2) & 0x3FFCu));
     const uint32_t off = ((c >> 10) ^ (p >> 18)) & 0x3FFCu;
     const uint32_t e = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(gt + 4096) + off);
     return __builtin_amdgcn_bitop3_b32(p, e, 0x000F0F0Fu, 0x28);  // (p ^ e) & mask
   };
+#endif
   // f16 subnormal pair: byte e0 of lo (0x0c: zero), byte e1 of hi, in halves 0 and 1
   auto pair = [](uint32_t hi, uint32_t lo, int e0, int e1) -> uint32_t {
     const uint32_t s0 = e0 < 0 ? 0x0cu : (uint32_t)e0, s1 = e1 < 0 ? 0x0cu : (uint32_t)(4 + e1);
@@ -194,6 +222,15 @@
       uint32_t sp[KC];
 #pragma unroll
       for (int c = 0; c < KC; ++c) sp[c] = sp_of(cw[c]);
+#ifdef ATTN_BODY_STATS  // [statistics] K: lane (n, g) holds codewords KC g .. KC g + KC - 1 of token n's row, once
+      if (counts && rows[i0 + 16 * tau + n] >= 0) {  // not a -1 block's / a past row's row 0
+        uint32_t f = 0;  // <= 12 codewords
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+          if (c < GC - 3 * KC || g < 3) f += sp[c] >> 24;  // group 3's tail: codewords >= 43 are the next row's
+        fold(f);
+      }
+#endif
       S[tau] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk) {
@@ -257,6 +294,15 @@
       }
 #pragma unroll
       for (int c = 0; c < VC; ++c) sv[j][c] = sp_of(vw[j][c]);
+#ifdef ATTN_BODY_STATS  // [statistics] V: lane n holds codewords 3n .. 3n + 2 of its 8 rows, once (lanes 14-15: >= 43)
+      if (counts && rv[j] >= 0) {
+        uint32_t f = 0;
+#pragma unroll
+        for (int c = 0; c < VC; ++c)
+          if (VC * n + c < GC) f += sv[j][c] >> 24;
+        fold(f);
+      }
+#endif
     }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -321,6 +367,12 @@
       ws_put(ws + 1, L);
     }
   }
+#ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
+  if (counts) {
+    const uint32_t cnt[2] = {n_bits, n_unc};
+    flush_stats_n<2>(a.stats, cnt);
+  }
+#endif
 #if !ATTN_BODY_CHUNK  // the counted combine: decode kernels only (chunk calls always launch the combine)
   if (a.ctr) combine_if_last<__half, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));
 #endif

@@ -8,6 +8,8 @@
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
 // The counted kernels (paged_attn_split_stats*_kernel, `a` a StatsArgs / StatsInterpArgs) also
 // define ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
+// So do the Golay counted kernels (paged_attn_split_golay_stats_kernel, `a` a StatsArgs, ATTN_BODY_CHUNK 1):
+// their counters hold bits corrected / uncorrectable words (Chunk::count) under the same names.
   constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
   using C = Chunk<CODEC, VEC>;
   constexpr int E = C::E;
@@ -234,10 +236,20 @@
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (live && ok[u]) {  // not the idle lanes' copy of lane 0, nor a -1 block's / a past row's row 0
+          if constexpr (is_golay(CODEC)) {
+            // the row's own codewords only: a lane's words past g - 1 are the next row's, the pad bytes' or 0
+            uint32_t f = 0;  // the count fields of <= 2 VEC codewords (Chunk::count)
 #pragma unroll
-          for (int k = 0; k < VEC; ++k) {
-            h84_count4(kc[u].w[k], n_single, n_double);
-            h84_count4(vc[u].w[k], n_single, n_double);
+            for (int k = 0; k < VEC; ++k)
+              if (VEC * c + k < a.g) f += kc[u].count(gtab, k) + vc[u].count(gtab, k);
+            n_single += f & 0x3Fu;  // bits corrected
+            n_double += f >> 6;     // uncorrectable words
+          } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+              h84_count4(kc[u].w[k], n_single, n_double);
+              h84_count4(vc[u].w[k], n_single, n_double);
+            }
           }
         }
         ok[u] = ok[u] && i0 + u * TP < ntok_att;  // rows past the row's own key limit: counted, not attended

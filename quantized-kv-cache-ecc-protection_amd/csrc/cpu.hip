@@ -1292,4 +1292,75 @@ KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch
   return KVECC_OK;
 }
 
+// Golay counted twin (kvecc_paged_attention_golay_stats): the ragged twin's output (q_spans may be
+// null), and the decoder's count of each of the g codewords of every K and V row of the first n_b
+// positions of each sequence that has a valid query token -- once per (sequence, cache head):
+// stats[0] += the counts 0..3 (bits corrected), stats[1] += the words of count 4 (uncorrectable).
+// Bits 24-31 of an int32 word and a packed row's pad bytes take no part (golay_decode1).
+KVECC_API int kvecc_cpu_paged_attention_golay_stats(const void *query, int64_t q_batch_stride,
+                                                    int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                                    const void *k_cache, const void *v_cache,
+                                                    const int32_t *block_table, const int32_t *context_lens,
+                                                    const int32_t *q_spans, const float *k_scales,
+                                                    const float *v_scales, void *out, int64_t batch,
+                                                    int64_t q_max, int64_t heads, int64_t kv_heads,
+                                                    int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                                    int64_t layer, int64_t block_size, int64_t max_blocks,
+                                                    int64_t max_context_len, float sm_scale, int codec,
+                                                    uint64_t *stats, int threads) {
+  if (!stats) return set_error(KVECC_EINVAL, "cpu_paged_attention_golay_stats: null stats");
+  if (codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL,
+                     "cpu_paged_attention_golay_stats: codec %d (this counted twin needs golay or golay_packed)", codec);
+  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_golay_stats: negative q_max");
+  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
+      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_golay_stats: bad query strides");
+  const int rc = cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, threads, q_spans);
+  if (rc != KVECC_OK || batch == 0 || heads == 0 || q_max == 0) return rc;
+  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
+  static uint16_t tab[8192];
+  static bool ready = [] {
+    build_golay_parity_table(tab);
+    build_golay_correct_table(tab + 4096);
+    return true;
+  }();
+  (void)ready;
+  const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
+  const int64_t g = (head_dim + 2) / 3;
+  uint64_t bits = 0, unc = 0;
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_max;
+    if (first < 0 || count <= 0 || first >= q_max) continue;  // all padding: the sequence is not read
+    const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
+    for (int64_t pos = 0; pos < nb; ++pos) {
+      const int32_t blk = block_table[b * max_blocks + pos / block_size];
+      if (blk < 0) continue;
+      for (int64_t hk = 0; hk < kv_heads; ++hk) {
+        const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
+        for (const void *cache : {k_cache, v_cache}) {
+          for (int64_t k = 0; k < g; ++k) {
+            uint32_t cnt, w;
+            if (packed) {
+              const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * KVECC_GOLAY_PACKED_ROW(g) + 3 * k;
+              w = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+            } else {
+              w = (uint32_t)reinterpret_cast<const int32_t *>(cache)[srow * g + k];
+            }
+            golay_decode1(w, tab, tab + 4096, cnt);
+            bits += cnt & 3u;
+            unc += cnt >> 2;
+          }
+        }
+      }
+    }
+  }
+  stats[0] += bits;
+  stats[1] += unc;
+  return KVECC_OK;
+}
+
 }  // extern "C"

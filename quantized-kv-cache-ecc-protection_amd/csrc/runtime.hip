@@ -153,9 +153,12 @@ static int ensure_tables(int d) {
     // the attention split kernels' variant, for words holding codeword << 2:
     // data nibbles at bits 0-3, 8-11 and 28-31, parity(lo) at bits 14-25 --
     // where such a word holds the received parity -- so the syndrome's byte
-    // offset is one masked XOR and a shift
+    // offset is one masked XOR and a shift.  The correction half carries the
+    // count field of `attn` in bits 16-23, for the counted kernels
+    // (Chunk::count): every other reader takes the entry through the nibble
+    // mask 0xF0000F0F, and the syndrome's offset comes from the parity half alone
     host.attn_x[i] = spread12x(i) | (uint32_t)host.par[i] << 14;
-    host.attn_x[4096 + i] = spread12x(host.cor[i] & 0xFFFu);
+    host.attn_x[4096 + i] = spread12x(host.cor[i] & 0xFFFu) | ((n & 3u) | (n >> 2) << 6) << 16;
     host.pk0[i] = (uint16_t)(host.par[i] << 2);
     host.pk1[i] = (host.cor[i] & 0xFFFu) | (n & 3u) << 24 | (n >> 2) << 31;
   }

@@ -20,13 +20,15 @@ from .ops import (cache_scrub, fused_decode_dequantize_hamming84, fused_quantize
                   inject_bit_errors_triton, inject_bit_errors_triton_batched,
                   inject_bit_errors_triton_vectorized, interpolate_double_errors,
                   interpolate_double_errors_1d, interpolate_double_errors_autotuned,
-                  paged_attention_chunk, paged_attention_ecc, query_spans, query_spans_from_mask)
+                  paged_attention_chunk, paged_attention_counted, paged_attention_counted_into,
+                  paged_attention_ecc, query_spans, query_spans_from_mask)
 from . import torch_ops  # noqa: F401  -- registers torch.ops.kvecc.* (CPU + HIP kernels, fake kernels)
 
 __version__ = "0.1.0"
 
 __all__ = [
-    "paged_attention_ecc", "paged_attention_chunk", "query_spans", "query_spans_from_mask", "cache_scrub",
+    "paged_attention_ecc", "paged_attention_chunk", "paged_attention_counted", "paged_attention_counted_into",
+    "query_spans", "query_spans_from_mask", "cache_scrub",
     "get_physical_dtype", "get_codeword_bits", "get_data_bits",
     "HAMMING74_BLOCK_SIZE", "HAMMING84_BLOCK_SIZE", "GOLAY_BLOCK_SIZE",
     "FAULT_INJECTION_BLOCK_SIZE", "INTERPOLATION_BLOCK_SIZE",

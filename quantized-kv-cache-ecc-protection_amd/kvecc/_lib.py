@@ -82,6 +82,9 @@ SIGNATURES = {
     "kvecc_paged_attention_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                     _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int,
                                     _vp, _vp, _i64, _vp],
+    "kvecc_paged_attention_golay_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                          _f32, _int, _vp, _vp, _i64, _vp],
     "kvecc_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                           _int, _vp, _vp],
     "kvecc_cpu_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -129,6 +132,9 @@ SIGNATURES = {
     "kvecc_cpu_paged_attention_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                         _f32, _int, _int, _vp, _int],
+    "kvecc_cpu_paged_attention_golay_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                              _i64, _f32, _int, _vp, _int],
 }
 _RESTYPE = {
     "kvecc_version": ctypes.c_char_p,

@@ -30,8 +30,10 @@ FUNCTIONS = (
 # ("hip", "cpu") both provide; a registered third-party backend may lack them
 # (the shim then raises where it needs one): the in-place cache scrub, and the
 # paged attention entries (paged_attention_chunk_into takes interp=True: the
-# interpolating attention of ECCShimConfig(interp_attention=True)).
-NATIVE_FUNCTIONS = ("cache_scrub_tensors", "paged_attention_into", "paged_attention_chunk_into")
+# interpolating attention of ECCShimConfig(interp_attention=True);
+# paged_attention_counted_into: the counted attention of counted_attention=True).
+NATIVE_FUNCTIONS = ("cache_scrub_tensors", "paged_attention_into", "paged_attention_chunk_into",
+                    "paged_attention_counted_into")
 
 # backend name -> module implementing FUNCTIONS
 CODEC_BACKENDS = {

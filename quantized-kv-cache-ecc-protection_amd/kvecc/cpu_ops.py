@@ -689,6 +689,52 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     return out
 
 
+def paged_attention_counted_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, layer_idx, block_size, sm_scale, codec, stats, max_context_len=0,
+                                 q_spans=None, interp=False):
+    """Host twin of ops.paged_attention_counted_into (same arguments and checks)."""
+    from .ops import _check_attention_chunk_args, _check_counted_codec, _check_q_spans
+    _check_counted_codec(codec, interp)
+    if stats is None:
+        raise ValueError("paged_attention_counted_into needs a stats buffer (cpu_ops.new_stats)")
+    if codec == "hamming84":
+        return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                          out, layer_idx, block_size, sm_scale, codec,
+                                          max_context_len=max_context_len, q_spans=q_spans, interp=interp,
+                                          stats=stats)
+    _check_cpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
+            or stats.numel() < 2 or stats.device.type != "cpu"):
+        raise ValueError("stats must be a contiguous int64 host tensor of >= 2 elements (cpu_ops.new_stats), got "
+                         f"{getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
+                         f"on {getattr(stats, 'device', None)}")
+    batch, q_len, heads, head_dim = query.shape
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    max_blocks = block_table.shape[1]
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
+    _lib.call("kvecc_cpu_paged_attention_golay_stats", _ptr(query), query.stride(0), query.stride(1),
+              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+              int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], _ptr(stats), NUM_THREADS)
+    return out
+
+
+def paged_attention_counted(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                            layer_idx, block_size, stats, sm_scale=None, codec="golay", max_context_len=0,
+                            q_spans=None, interp=False):
+    """Host twin of ops.paged_attention_counted: a fresh [B, q_len, H, D] output."""
+    if sm_scale is None:
+        sm_scale = 1.0 / math.sqrt(query.shape[-1])
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    return paged_attention_counted_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                        out, layer_idx, block_size, sm_scale, codec, stats,
+                                        max_context_len=max_context_len, q_spans=q_spans, interp=interp)
+
+
 def paged_attention_ecc(query, k_cache, v_cache, block_table, context_lens, k_scales, layer_idx,
                         block_size, sm_scale=None, codec="hamming84", syndrome_table=None,
                         use_tiled=False, block_m=4, v_scales=None):

@@ -147,6 +147,14 @@ class ECCShimConfig:
     difference: with held spans, a sequence that has no valid
     token in the forward is not read and so not counted, where the rectangular
     read counts it.
+    ``counted_attention`` (append mode, hamming84 or golay with either
+    golay_storage, opt-in) is that route whatever the protected codec: for
+    hamming84 it is ``stats_attention`` itself (interpolation included); for
+    golay every forward of ``_append_attend`` -- every q_len, every held span --
+    goes through kvecc_paged_attention_golay_stats when head_dim <= 256, which
+    adds the bits corrected / uncorrectable words of the codewords it reads to
+    the shim's statistics, exactly ``decode_stats=True``'s counts, with the same
+    precedence, fall-back and held-span difference as ``stats_attention``.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -158,7 +166,7 @@ class ECCShimConfig:
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
                  decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False,
-                 stats_attention=False):
+                 stats_attention=False, counted_attention=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -200,6 +208,10 @@ class ECCShimConfig:
             raise ValueError("stats_attention=True needs cache_mode='append' and codec='hamming84', "
                              f"not codec={codec!r}, cache_mode={cache_mode!r}")
         self.stats_attention = bool(stats_attention)
+        if counted_attention and (cache_mode != "append" or codec not in ("hamming84", "golay")):
+            raise ValueError("counted_attention=True needs cache_mode='append' and codec 'hamming84' or 'golay', "
+                             f"not codec={codec!r}, cache_mode={cache_mode!r}")
+        self.counted_attention = bool(counted_attention)
 
 
 class SimpleBlockManager:
@@ -681,7 +693,25 @@ class ECCBackend:
         interp = cfg.use_interpolation and cfg.codec == "hamming84"
         # hamming74 / int4 take the kernels only under kernel_attention (their codec is checked there)
         kernel_codec = cfg.codec in ("hamming84", "golay") or cfg.kernel_attention
-        if cfg.stats_attention and d <= 256:
+        if cfg.counted_attention and cfg.codec == "golay" and d <= 256:
+            # every q_len on the Golay counted kernels (int32 or packed rows): the bits
+            # corrected / uncorrectable words of the codewords read added to the shim's buffer
+            sp = None
+            if self._spans is not None:
+                self._check_spans(b, q_len)
+                sp = self._span_buf[:b]
+            qt = q.transpose(1, 2)
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention_golay_stats(
+                    qt, mgr.k_cache, mgr.v_cache, table, dev_lens, sp, mgr.k_scales, mgr.v_scales, self._stats,
+                    layer_idx, mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, ctx)
+                return out.transpose(1, 2)
+            out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+            self.codec_backend.paged_attention_counted_into(
+                qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, self._stats, max_context_len=ctx, q_spans=sp)
+            return out.transpose(1, 2)
+        if (cfg.stats_attention or cfg.counted_attention) and d <= 256:  # (counted_attention: hamming84 here)
             # every q_len on the counted kernels: q read in place as [batch, q_len,
             # heads, d], the decode statistics of the bytes read added to the shim's
             # buffer, doubles interpolated inline iff use_interpolation

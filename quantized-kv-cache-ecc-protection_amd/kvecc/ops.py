@@ -1335,6 +1335,79 @@ def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_
                                       stats=stats)
 
 
+_GOLAY_CODECS = ("golay", "golay_packed")
+
+
+def _check_counted_codec(codec, interp):
+    """The codecs the attention kernels count for (paged_attention_counted*)."""
+    if codec in _GOLAY_CODECS:
+        if interp:
+            raise ValueError(f"interp needs hamming84 (no Golay word is interpolated), got codec {codec!r}")
+    elif codec != "hamming84":
+        raise ValueError("the counted attention kernels serve hamming84, golay and golay_packed, "
+                         f"got codec {codec!r}")
+
+
+def paged_attention_counted_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, layer_idx, block_size, sm_scale, codec, stats, max_context_len=0,
+                                 q_spans=None, interp=False):
+    """Paged attention on the counted kernels, whatever the protected codec:
+    paged_attention_chunk_into's arguments and a required `stats` (an
+    ops.new_stats buffer on the query's device), to which the decode statistics
+    of every stored K and V word of each sequence that has a valid token are
+    added exactly once, as shim_read(ctx = n_b, stats) counts them.
+
+    "golay" / "golay_packed": kvecc_paged_attention_golay_stats (stats[0] += bits
+    corrected, stats[1] += uncorrectable words); interp=True is a ValueError.
+    "hamming84": paged_attention_chunk_into(..., stats=), unchanged.
+    "hamming74" / "int4": ValueError (their kernels keep no count)."""
+    _check_counted_codec(codec, interp)
+    if stats is None:
+        raise ValueError("paged_attention_counted_into needs a stats buffer (ops.new_stats)")
+    if codec == "hamming84":
+        return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                          out, layer_idx, block_size, sm_scale, codec,
+                                          max_context_len=max_context_len, q_spans=q_spans, interp=interp,
+                                          stats=stats)
+    _check_gpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    sp = _sptr(stats, query.device)
+    batch, q_len, heads, head_dim = query.shape
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    max_blocks = block_table.shape[1]
+    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
+    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
+    ws = _attn_workspace(query.device, ws_n)
+    _lib.call("kvecc_paged_attention_golay_stats", _ptr(query), query.stride(0), query.stride(1),
+              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+              mcl, float(sm_scale), SHIM_CODECS[codec], sp, _ptr(ws), ws.numel(), _stream(query.device))
+    return out
+
+
+def paged_attention_counted(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                            layer_idx, block_size, stats, sm_scale=None, codec="golay", max_context_len=0,
+                            q_spans=None, interp=False):
+    """paged_attention_counted_into with a fresh [B, q_len, H, D] output; on the
+    GPU or, for host tensors, through the host twin."""
+    if sm_scale is None:
+        sm_scale = 1.0 / math.sqrt(query.shape[-1])
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    if query.device.type == "cpu":
+        from . import cpu_ops
+        return cpu_ops.paged_attention_counted_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
+                                                    v_scales, out, layer_idx, block_size, sm_scale, codec, stats,
+                                                    max_context_len=max_context_len, q_spans=q_spans,
+                                                    interp=interp)
+    return paged_attention_counted_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                        out, layer_idx, block_size, sm_scale, codec, stats,
+                                        max_context_len=max_context_len, q_spans=q_spans, interp=interp)
+
+
 def _conform(t, dtype):
     """t itself when it already has dtype and is contiguous (no copy)."""
     if t.dtype != dtype:

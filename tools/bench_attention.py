@@ -32,6 +32,8 @@ hamming74 and hamming84 on clean encoded caches of the same nibbles, hamming74 a
 injected at BER 1e-3, and shim_read_batch + repeat_interleave + masked SDPA over the int4 and
 hamming74 caches, the path ECCShimConfig(kernel_attention=True) replaces.
 
+--stats --codec golay | golay_packed times the Golay counted entry (kvecc_paged_attention_golay_stats)
+against the uncounted Golay kernels and the counting read + masked SDPA (bench_golay_stats).
 --stats times the counted entry (kvecc_paged_attention_stats, Hamming(8,4)) in one process at
 --kv-heads and --heads / 4 cache heads, q_len 1 and 16, on a clean encoded cache and on one injected
 at BER 1e-3, one JSON line per case, every pass visiting the cases in turn: the counted entry with
@@ -450,8 +452,10 @@ def bench_stats(args, ops, dev):
 
     import torch.nn.functional as F
     from kvecc.memory_layout import kv_cache_pair
+    if args.codec in ("golay", "golay_packed"):
+        return bench_golay_stats(args, ops, dev)
     if args.codec != "hamming84":
-        raise SystemExit("--stats needs --codec hamming84")
+        raise SystemExit("--stats needs --codec hamming84, golay or golay_packed")
     g = torch.Generator(device=dev).manual_seed(0)
     nb = (args.ctx + args.bs - 1) // args.bs
     blocks = args.batch * nb
@@ -538,6 +542,114 @@ def bench_stats(args, ops, dev):
                 print(json.dumps({"kernel": "paged_attention_stats", "batch": args.batch, "q_len": n,
                                   "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
                                   "block_size": args.bs, "ber": ber, "counts_per_call": totals, **res}), flush=True)
+            del kc, vc
+        del x
+
+
+def bench_golay_stats(args, ops, dev):
+    """--stats --codec golay | golay_packed: the counted kernels (kvecc_paged_attention_golay_stats), the
+    uncounted Golay kernels and the counting shim_read_batch + masked SDPA that
+    ECCShimConfig(counted_attention=True) replaces, alternated in one process; clean and BER 1e-2;
+    --kv-heads and --heads / 4 cache heads; q_len 1 and 16."""
+    import statistics
+    import time
+
+    import torch.nn.functional as F
+    from kvecc.memory_layout import kv_cache_pair
+    codec = args.codec
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    sm = 1 / math.sqrt(args.d)
+    gg = (args.d + 2) // 3
+    per = gg if codec == "golay" else (3 * gg + 3) // 4 * 4
+
+    def timed_alternating(cases):
+        for fn in cases.values():
+            t0 = time.perf_counter()
+            while True:
+                for _ in range(args.warmup):
+                    fn()
+                torch.cuda.synchronize()
+                if time.perf_counter() - t0 >= args.warmup_s:
+                    break
+        passes = {name: [] for name in cases}
+        for _ in range(args.passes):
+            for name, fn in cases.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                passes[name].append(e0.elapsed_time(e1) / args.iters * 1e3)
+        return {name: {"us_per_call": round(statistics.median(p), 2), "pass_us": [round(x, 2) for x in p],
+                       "spread_us": round(max(p) - min(p), 2)} for name, p in passes.items()}
+
+    for kvh in (args.kv_heads, max(1, args.heads // 4)):
+        x = torch.randint(0, 16, (2, blocks, 1, kvh, args.bs, args.d), device=dev, generator=g, dtype=torch.uint8)
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        groups = args.heads // kvh
+        for ber in (0.0, 1e-2):
+            kc, vc = kv_cache_pair((blocks, 1, kvh, args.bs * per), torch.int32 if codec == "golay" else torch.uint8,
+                                   dev)
+            for side, dst in enumerate((kc, vc)):
+                cw = ops.golay_encode_rows(x[side]).view(-1)
+                if ber > 0:
+                    ops.inject_into(cw, cw, ber, 24, seed=42 + side)
+                if codec == "golay":
+                    dst.view(-1).copy_(cw)
+                else:  # 3 bytes per codeword, rows padded to KVECC_GOLAY_PACKED_ROW
+                    dst.zero_()
+                    b3 = torch.stack([(cw >> (8 * k)) & 0xFF for k in range(3)], -1).to(torch.uint8)
+                    dst.view(blocks, 1, kvh, args.bs, per)[..., :3 * gg].copy_(b3.view(blocks, 1, kvh, args.bs, 3 * gg))
+            for n in (1, 16):
+                qc = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half()
+                qt = qc.transpose(1, 2)
+                q1 = qc[:, :, 0].contiguous()
+                outc = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+                out1 = torch.empty_like(q1)
+                stats = ops.new_stats(dev)
+
+                def counted():
+                    ops.paged_attention_counted_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm, codec,
+                                                     stats, args.ctx)
+
+                def uncounted():
+                    if n == 1:
+                        ops.paged_attention_into(q1, kc, vc, table, lens, ks, vs, out1, 0, args.bs, sm, codec,
+                                                 args.ctx)
+                    else:
+                        ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm, codec,
+                                                       args.ctx)
+
+                def read_sdpa():
+                    k_t, v_t = ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, codec, qc.dtype,
+                                                   stats=stats)
+                    if groups > 1:
+                        k_t = k_t.repeat_interleave(groups, dim=1)
+                        v_t = v_t.repeat_interleave(groups, dim=1)
+                    qpos = (lens - n).view(-1, 1, 1) + torch.arange(n, device=dev).view(1, n, 1)
+                    mask = torch.arange(args.ctx, device=dev).view(1, 1, args.ctx) <= qpos
+                    return F.scaled_dot_product_attention(qc, k_t, v_t, attn_mask=mask.unsqueeze(1))
+
+                # one counted call's totals against one counting read's: the same codewords, counted alike
+                ref = ops.new_stats(dev)
+                ops.shim_read_batch(kc, vc, ks, vs, table, args.ctx, args.d, 0, codec, qc.dtype, stats=ref)
+                counted()
+                totals = ops.read_stats(stats)
+                assert totals == ops.read_stats(ref), (totals, ops.read_stats(ref))
+                res = timed_alternating({"counted": counted, "uncounted": uncounted, "read_stats_sdpa": read_sdpa})
+                res["counting_cost_us"] = round(res["counted"]["us_per_call"] - res["uncounted"]["us_per_call"], 2)
+                res["read_sdpa_over_counted"] = round(res["read_stats_sdpa"]["us_per_call"] /
+                                                      res["counted"]["us_per_call"], 2)
+                print(json.dumps({"kernel": "paged_attention_golay_stats", "codec": codec, "batch": args.batch,
+                                  "q_len": n, "heads": args.heads, "kv_heads": kvh, "head_dim": args.d,
+                                  "ctx": args.ctx, "block_size": args.bs, "ber": ber, "counts_per_call": totals,
+                                  **res}), flush=True)
             del kc, vc
         del x
 
