@@ -658,6 +658,73 @@ KVECC_API int kvecc_paged_attention_golay_stats(const void *query, int64_t q_bat
                                                 uint64_t *stats, float *workspace, int64_t workspace_floats,
                                                 void *stream);
 
+/* ---- Repairing attention ----------------------------------------------------- */
+/* kvecc_paged_attention_stats that also writes the corrected codewords back
+ * (read-repair; no reference counterpart): one launch attends, counts and
+ * scrubs what it counts.  The arguments are kvecc_paged_attention_stats's,
+ * interp and stats included, except that k_cache / v_cache are NOT const: they
+ * are the only arguments written besides out, stats and the workspace.
+ * Validation is the counted entry's: KVECC_CODEC_H84 only, caches and scale
+ * arrays under 4 GiB, stats non-NULL -- anything else is KVECC_EINVAL with a
+ * message that names paged_attention_repair, and nothing is launched or
+ * written.  The launch path reads nothing on the host: the call replays in a
+ * captured graph.
+ *
+ * With n_b = min(context_lens[b], max_context_len, max_blocks*block_size) as in
+ * "Counted attention":
+ *
+ * Output.  Bit for bit what kvecc_paged_attention_stats writes for the same
+ * arguments on the cache as it stood before the call, in both interp modes: the
+ * launcher picks the counted entry's geometry and the kernels run its
+ * arithmetic stream.  This is derivable, not a tolerance: a rewritten byte
+ * decodes to the same nibble as the byte it replaces (type 1: the corrected
+ * nibble; type 3: the data bits were never wrong), a double is never rewritten
+ * -- so its type, the one thing interpolation looks at besides decoded nibbles,
+ * never changes -- and interpolation reads its neighbours' DECODED nibbles.  So
+ * whether a concurrently reading workgroup (another query-head group of the
+ * cache head, another token tile or query row, an interpolation halo) sees the
+ * old or the new byte cannot matter.
+ *
+ * Statistics.  stats[0] / stats[1] += exactly what the counted entry adds;
+ * stats[2] += the number of bytes rewritten.
+ *
+ * Cache after the call.  What kvecc_cache_scrub leaves of the cache as it stood
+ * before the call when run with layer_first = layer, layer_count = 1, the same
+ * clamp, and the length of every sequence without a valid query token set to 0:
+ * for layer `layer`, each sequence with at least one valid query token, each
+ * cache head, K and V, each position l < n_b whose block-table entry is >= 0, a
+ * type-1 (single) or type-3 (overall parity) byte becomes encode(decoded data);
+ * type-2 and clean bytes stay bit for bit (h84_scrub4 of csrc/codec_math.h).
+ * Every other byte of both caches keeps its bits: other layers, positions >=
+ * n_b, -1 blocks, blocks no counted row names, all-padding sequences, and the
+ * row-0 stand-ins that masked lanes read.  Both scale arrays keep theirs.
+ * stats[2] equals that scrub's stats[2].  A call over a clean or already
+ * repaired region stores nothing.  Two table rows may name the same block: the
+ * bytes come out as the scrub's (every writer stores the same value), but a
+ * byte of that block may then be counted in stats[0] / stats[2] by one row
+ * before and by the other after it was rewritten, so those two totals are only
+ * bounded by the counted entry's / the scrub's.
+ *
+ * Kernels.  Repairing siblings of the 126 counted Hamming(8,4) kernels, under
+ * their own names.  Only the counting workgroup of each (sequence, cache head,
+ * context split) stores, where it counts and on the words as loaded -- before the
+ * interpolating kernels rewrite any in registers.  There each stored byte of
+ * the first n_b positions is held by exactly one lane, once per call; a lane
+ * stores a word (head_dim 32's V chunk: its two bytes) only if the XOR of
+ * h84_scrub4 is non-zero, with a plain vector buffer store through the
+ * descriptor the word was loaded through.  No fence and no atomic touches the
+ * cache; kernel completion publishes the stores. */
+KVECC_API int kvecc_paged_attention_repair(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                           int64_t q_head_stride, int q_dtype, void *k_cache, void *v_cache,
+                                           const int32_t *block_table, const int32_t *context_lens,
+                                           const int32_t *q_spans, const float *k_scales,
+                                           const float *v_scales, void *out, int64_t batch, int64_t q_max,
+                                           int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                           int64_t num_blocks, int64_t num_layers, int64_t layer,
+                                           int64_t block_size, int64_t max_blocks, int64_t max_context_len,
+                                           float sm_scale, int codec, int interp, uint64_t *stats,
+                                           float *workspace, int64_t workspace_floats, void *stream);
+
 /* ---- Cache scrub --------------------------------------------------------------- */
 /* In-place patrol scrub of a resident paged cache (no reference counterpart:
  * the reference's cache lives for one forward, and every reader here corrects
@@ -858,6 +925,19 @@ KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch
                                               int64_t layer, int64_t block_size, int64_t max_blocks,
                                               int64_t max_context_len, float sm_scale, int codec, int interp,
                                               uint64_t *stats, int threads);
+/* host twin of kvecc_paged_attention_repair: the host counted twin's output (computed on the cache
+ * as it stood) and counts, then h84_scrub4 over the same region of the HOST caches, which it
+ * writes; stats a host buffer of >= 3 words, word 2 += bytes rewritten */
+KVECC_API int kvecc_cpu_paged_attention_repair(const void *query, int64_t q_batch_stride,
+                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                               void *k_cache, void *v_cache, const int32_t *block_table,
+                                               const int32_t *context_lens, const int32_t *q_spans,
+                                               const float *k_scales, const float *v_scales, void *out,
+                                               int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                               int64_t layer, int64_t block_size, int64_t max_blocks,
+                                               int64_t max_context_len, float sm_scale, int codec, int interp,
+                                               uint64_t *stats, int threads);
 /* host twin of kvecc_paged_attention_golay_stats (as above) */
 KVECC_API int kvecc_cpu_paged_attention_golay_stats(const void *query, int64_t q_batch_stride,
                                                     int64_t q_token_stride, int64_t q_head_stride, int q_dtype,

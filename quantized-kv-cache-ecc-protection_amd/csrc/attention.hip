@@ -190,6 +190,18 @@ struct StatsInterpArgs : InterpArgs {
 template <typename A>
 constexpr bool is_stats = std::is_same<A, StatsArgs>::value || std::is_same<A, StatsInterpArgs>::value;
 
+// Repairing calls (kvecc_paged_attention_repair, Hamming(8,4) only) run further
+// kernels of their own names: the counted kernels' text plus the [repair]
+// islands, in which the counting workgroup stores the corrected codewords back
+// through the cache descriptors (kvecc.h "Repairing attention").  Their blocks
+// add nothing to the counted ones -- stats word 2 takes the rewritten bytes -- and
+// are types of their own so that the counted kernels keep their names, their
+// text and their registers.
+struct RepairArgs : StatsArgs {};
+struct RepairInterpArgs : StatsInterpArgs {};
+template <typename A>
+constexpr bool is_repair = std::is_same<A, RepairArgs>::value || std::is_same<A, RepairInterpArgs>::value;
+
 // Byte caches without SECDED (KVECC_CODEC_H74, KVECC_CODEC_NONE: Hamming(8,4)'s
 // layout, uint8, one value per byte, rows of head_dim bytes) run one sibling
 // family of kernels, of their own names, over the Hamming(8,4) bodies: every
@@ -249,6 +261,27 @@ __device__ __forceinline__ void h84_count4(uint32_t w, uint32_t &n_single, uint3
   const uint32_t nz = ((c & 0x07070707u) + 0x07070707u) & 0x08080808u;
   n_single += __builtin_popcount(nz & (c >> 1));
   n_double += __builtin_popcount(nz & ~(c >> 1));
+}
+// The repairing kernels' store of one counted word: h84_repair4 (codec_math.h:
+// h84_scrub4's XOR and counts from the first look's h_code4, without the decode /
+// re-encode round trip) counts its four bytes as h84_count4 does, and the bytes it
+// rewrites, and gives the XOR to the word the scrubber would leave -- singles and
+// parity-only bytes become encode(decoded data), doubles and clean bytes 0 --
+// which goes back through the descriptor the word came through, at the offset it
+// came from, only if some byte changes.  A plain vector store: what a concurrent
+// reader sees, old byte or new, decodes to the same nibble (kvecc.h "Repairing
+// attention").
+// NB 4: the whole dword; NB 2: its low two bytes (head_dim 32's V chunk).
+template <int NB = 4>
+__device__ __forceinline__ void h84_repair_store(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t w,
+                                                 uint32_t &n_single, uint32_t &n_double, uint32_t &n_rewritten) {
+  const uint32_t x = h84_repair4(w, n_single, n_double, n_rewritten);
+  if (x) {
+    if constexpr (NB == 2)
+      __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(w ^ x), rs, off, 0, 0);
+    else
+      __builtin_amdgcn_raw_buffer_store_b32(w ^ x, rs, off, 0, 0);
+  }
 }
 // ... and their slow path: four codewords decoded, the doubles replaced by
 // interp_word of the neighbours' decoded (not interpolated) values wl / wr, and
@@ -690,6 +723,32 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_stats_interp_kernel(S
 #undef ATTN_BODY_STATS
 #undef ATTN_BODY_CHUNK
 }
+// the repairing entry's kernels (kvecc_paged_attention_repair): the counted kernels' two forms with the
+// [repair] islands as well
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_repair_kernel(RepairArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_STATS 1
+#define ATTN_BODY_REPAIR 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_REPAIR
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_repair_interp_kernel(RepairInterpArgs a) {
+  constexpr int CODEC = KVECC_CODEC_H84, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 2
+#define ATTN_BODY_STATS 1
+#define ATTN_BODY_REPAIR 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_REPAIR
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
 // the Golay counted entry's kernels (kvecc_paged_attention_golay_stats): the chunk form with the
 // [statistics] islands, int32 and packed caches, buffer-addressed only
 template <typename T, int CODEC, int VEC, int W, int G = 1>
@@ -926,6 +985,30 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_stats_kernel(St
 #undef ATTN_BODY_STATS
 #undef ATTN_BODY_CHUNK
 }
+// the repairing entry's (kvecc_paged_attention_repair): the counted kernels' two forms with the [repair]
+// islands as well
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_repair_interp_kernel(RepairInterpArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_STATS 1
+#define ATTN_BODY_REPAIR 1
+#include "attn_h84_mfma_interp_body.inc"
+#undef ATTN_BODY_REPAIR
+#undef ATTN_BODY_STATS
+}
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_repair_kernel(RepairArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_STATS 1
+#define ATTN_BODY_REPAIR 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_REPAIR
+#undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
 // the byte family's: the decode, chunk and ragged kernels over the same body
 template <int D, int G>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_byte_mfma_kernel(ByteAttnArgs a) {
@@ -1028,6 +1111,11 @@ static int pow2_at_least(int64_t x) {
         KVECC_LAUNCH((paged_attn_split_byte_chunk_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
       else if constexpr (CODEC == KVECC_CODEC_H84)                                                              \
         KVECC_LAUNCH((paged_attn_split_byte_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
+    } else if constexpr (is_repair<A>) {                                                                        \
+      if constexpr (CODEC == KVECC_CODEC_H84 && BUF_ && std::is_same<A, RepairInterpArgs>::value)               \
+        KVECC_LAUNCH((paged_attn_split_repair_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);   \
+      else if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                      \
+        KVECC_LAUNCH((paged_attn_split_repair_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
     } else if constexpr (is_stats<A>) {                                                                         \
       if constexpr (CODEC == KVECC_CODEC_H84 && BUF_ && std::is_same<A, StatsInterpArgs>::value)                \
         KVECC_LAUNCH((paged_attn_split_stats_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);    \
@@ -1324,13 +1412,18 @@ static int launch_mfma_interp(const InterpArgs &a, int64_t batch, int64_t tiles,
   launch_combine<__half>(a, batch * a.q_len, st);
   return KVECC_OK;
 }
-// the counted entry's matrix-core kernels (uniform calls too: the spans are nullable)
+// the counted entry's matrix-core kernels (uniform calls too: the spans are nullable), and the
+// repairing entry's (A RepairArgs / RepairInterpArgs): the same grid
 template <typename A>
 static int launch_mfma_stats(const A &a, int64_t batch, int64_t tiles, hipStream_t st) {
   const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
 #define KVECC_MFMA_STATS_LAUNCH(D_)                                                                  \
   do {                                                                                               \
-    if constexpr (std::is_same<A, StatsInterpArgs>::value)                                           \
+    if constexpr (std::is_same<A, RepairInterpArgs>::value)                                          \
+      KVECC_LAUNCH((paged_attn_h84_mfma_repair_interp_kernel<D_>), grid, dim3(kBlock), 0, st, a);    \
+    else if constexpr (std::is_same<A, RepairArgs>::value)                                           \
+      KVECC_LAUNCH((paged_attn_h84_mfma_repair_kernel<D_>), grid, dim3(kBlock), 0, st, a);           \
+    else if constexpr (std::is_same<A, StatsInterpArgs>::value)                                      \
       KVECC_LAUNCH((paged_attn_h84_mfma_stats_interp_kernel<D_>), grid, dim3(kBlock), 0, st, a);     \
     else                                                                                             \
       KVECC_LAUNCH((paged_attn_h84_mfma_stats_kernel<D_>), grid, dim3(kBlock), 0, st, a);            \
@@ -1374,8 +1467,8 @@ static int launch_golay_stats_rows(int codec, StatsArgs a, int64_t rows, int gq,
   return KVECC_OK;
 }
 // The Hamming(8,4) layout's general path: launch_codec_rows for the interpolating split kernels
-// (A InterpArgs), for the byte family's (A ByteChunkArgs) and for the counted
-// ones (A StatsArgs / StatsInterpArgs)
+// (A InterpArgs), for the byte family's (A ByteChunkArgs), for the counted
+// ones (A StatsArgs / StatsInterpArgs) and for the repairing ones (A RepairArgs / RepairInterpArgs)
 template <typename T, typename A>
 static int launch_h84_rows(A a, int64_t rows, int gq, hipStream_t st) {
   const int64_t wg_per_row = a.heads / gq;
@@ -1588,10 +1681,12 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
                                       int64_t block_size, int64_t max_blocks, int64_t max_context_len,
                                       float sm_scale, int codec, float *workspace, int64_t workspace_floats,
                                       void *stream, bool interp = false, uint64_t *stats = nullptr,
-                                      bool golay_stats = false) {
+                                      bool golay_stats = false, bool repair = false) {
   if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
   // golay_stats: kvecc_paged_attention_golay_stats, which has checked its codec and its buffer
+  // repair: kvecc_paged_attention_repair (stats non-null, hamming84: checked there), the counted call's
+  // geometry and argument values over the repairing kernels
   if (stats && !golay_stats && codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
   if (interp && codec != KVECC_CODEC_H84)
@@ -1686,7 +1781,9 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
     return set_error(KVECC_EINVAL, "paged_attention_interp: caches of 4 GiB or more are not supported");
   if (stats && !fits)
     return set_error(KVECC_EINVAL, "%s: caches of 4 GiB or more are not supported",
-                     golay_stats ? "paged_attention_golay_stats" : "paged_attention_stats");
+                     golay_stats ? "paged_attention_golay_stats"
+                     : repair    ? "paged_attention_repair"
+                                 : "paged_attention_stats");
   const int gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
   // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound);
   // an interpolating call takes its matrix-core kernels at q_len 1 too (one tile, the same bound: `finest`)
@@ -1750,6 +1847,28 @@ static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride,
         case KVECC_F32: rc = launch_golay_stats_rows<float>(codec, sa, vbatch, gq, st); break;
         case KVECC_F16: rc = launch_golay_stats_rows<__half>(codec, sa, vbatch, gq, st); break;
         default: rc = launch_golay_stats_rows<__hip_bfloat16>(codec, sa, vbatch, gq, st); break;
+      }
+    }
+  } else if (repair) {  // the repairing kernels' argument blocks: the counted ones' values
+    RepairArgs ra;
+    RepairInterpArgs ri;
+    static_cast<RaggedArgs &>(ra) = a;
+    static_cast<RaggedArgs &>(ri) = a;
+    ra.stats = ri.stats = stats;
+    if (gm) {
+      rc = interp ? launch_mfma_stats(ri, batch, tiles, st) : launch_mfma_stats(ra, batch, tiles, st);
+    } else {
+      switch (q_dtype) {
+        case KVECC_F32:
+          rc = interp ? launch_h84_rows<float>(ri, vbatch, gq, st) : launch_h84_rows<float>(ra, vbatch, gq, st);
+          break;
+        case KVECC_F16:
+          rc = interp ? launch_h84_rows<__half>(ri, vbatch, gq, st) : launch_h84_rows<__half>(ra, vbatch, gq, st);
+          break;
+        default:
+          rc = interp ? launch_h84_rows<__hip_bfloat16>(ri, vbatch, gq, st)
+                      : launch_h84_rows<__hip_bfloat16>(ra, vbatch, gq, st);
+          break;
       }
     }
   } else if (stats) {  // the counted kernels' argument blocks
@@ -1878,6 +1997,26 @@ KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_str
                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream,
                                     interp != 0, stats);
+}
+
+KVECC_API int kvecc_paged_attention_repair(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                           int64_t q_head_stride, int q_dtype, void *k_cache, void *v_cache,
+                                           const int32_t *block_table, const int32_t *context_lens,
+                                           const int32_t *q_spans, const float *k_scales,
+                                           const float *v_scales, void *out, int64_t batch, int64_t q_max,
+                                           int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                           int64_t num_blocks, int64_t num_layers, int64_t layer,
+                                           int64_t block_size, int64_t max_blocks, int64_t max_context_len,
+                                           float sm_scale, int codec, int interp, uint64_t *stats,
+                                           float *workspace, int64_t workspace_floats, void *stream) {
+  if (!stats) return set_error(KVECC_EINVAL, "paged_attention_repair: null stats");
+  if (codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "paged_attention_repair: codec %d (the repairing kernels need hamming84)", codec);
+  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream,
+                                    interp != 0, stats, false, true);
 }
 
 KVECC_API int kvecc_paged_attention_golay_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,

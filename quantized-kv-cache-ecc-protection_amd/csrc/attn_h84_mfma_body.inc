@@ -7,6 +7,9 @@
 // attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
 // The counted kernel (paged_attn_h84_mfma_stats_kernel, `a` a StatsArgs, the ragged form) also
 // defines ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
+// The repairing kernel (paged_attn_h84_mfma_repair_kernel, `a` a RepairArgs) defines ATTN_BODY_REPAIR
+// as well: the [repair] islands, in which the counting workgroup stores the corrected codewords back
+// where it counts them (kvecc.h "Repairing attention"); without it the text is the counted kernel's.
   constexpr int KK = D / 32;  // QK MFMAs per 16-token tile
   constexpr int MT = D / 16;  // PV M-tiles; V bytes per lane per token
   constexpr int KB = D / 4;   // K bytes per lane per token
@@ -40,6 +43,9 @@
                       h0 % (a.heads / a.kv_heads) == 0;
   const int64_t ctx = counts ? min<int64_t>(a.ctx_lens[b], a.ctx_cap) : cm.ctx;
   uint32_t n_single = 0, n_double = 0;
+#ifdef ATTN_BODY_REPAIR  // [repair] bytes rewritten: the statistics buffer's word 2
+  uint32_t n_rewritten = 0;
+#endif
 #else
   const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns
 #endif
@@ -158,7 +164,39 @@
     const float *ks = cur.ks, *vs = cur.vs;
     auto &kw = cur.kw;
     auto &vw = cur.vw;
-#ifdef ATTN_BODY_STATS  // [statistics] every lane's K and V words are its own: each stored byte once
+#ifdef ATTN_BODY_REPAIR  // [repair] the [statistics] island below, storing: only the counting workgroup,
+    // only rows it counts (never a masked lane's row 0), only words with a byte to rewrite.  A
+    // row's first look is the OR of its words' h_code4: a clean row counts and stores nothing.
+    if (counts) {
+#pragma unroll
+      for (int tau = 0; tau < 2; ++tau) {
+        const int32_t r = rows[i0 + 16 * tau + n];
+        uint32_t dirty = 0;
+#pragma unroll
+        for (int k = 0; k < KB / 4; ++k) dirty |= h_code4(kw[tau][k]);
+        if (r >= 0 && dirty) {
+          const uint32_t off = (uint32_t)r * (uint32_t)D + (uint32_t)(KB * g);  // load_step's
+#pragma unroll
+          for (int k = 0; k < KB / 4; ++k) h84_repair_store(krs, off + 4u * k, kw[tau][k], n_single, n_double, n_rewritten);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        uint32_t dirty = 0;
+#pragma unroll
+        for (int k = 0; k < VW; ++k) dirty |= h_code4(MT < 4 ? vw[j][k] & 0xFFFFu : vw[j][k]);
+        if (rv[j] >= 0 && dirty) {
+          const uint32_t off = (uint32_t)rv[j] * (uint32_t)D + (uint32_t)(MT * n);
+          if constexpr (MT < 4) {  // head_dim 32: the lane's two bytes, as a two-byte store
+            h84_repair_store<2>(vrs, off, vw[j][0] & 0xFFFFu, n_single, n_double, n_rewritten);
+          } else {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) h84_repair_store(vrs, off + 4u * k, vw[j][k], n_single, n_double, n_rewritten);
+          }
+        }
+      }
+    }
+#elif defined(ATTN_BODY_STATS)  // [statistics] every lane's K and V words are its own: each stored byte once
     if (counts) {
 #pragma unroll
       for (int tau = 0; tau < 2; ++tau) {
@@ -298,8 +336,13 @@
   }
 #ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
   if (counts) {
+#ifdef ATTN_BODY_REPAIR  // [repair] ... and a third for the bytes rewritten
+    const uint32_t cnt[3] = {n_single, n_double, n_rewritten};
+    flush_stats_n<3>(a.stats, cnt);
+#else
     const uint32_t cnt[2] = {n_single, n_double};
     flush_stats_n<2>(a.stats, cnt);
+#endif
   }
 #endif
 #if !ATTN_BODY_CHUNK  // the counted combine: decode kernels only (chunk calls always launch the combine)

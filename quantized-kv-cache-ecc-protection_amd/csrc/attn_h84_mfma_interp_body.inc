@@ -27,6 +27,10 @@
 // ATTN_BODY_STATS around its inclusion: the [statistics] islands, which count the words of
 // load_step -- every stored byte once -- and never the neighbour words of the slow path; without
 // it the preprocessed text is what it was.
+// The repairing kernel (paged_attn_h84_mfma_repair_interp_kernel, `a` a RepairInterpArgs) defines
+// ATTN_BODY_REPAIR as well: the [repair] islands, which store the corrected codewords of load_step's
+// words back before the slow path rewrites any in registers -- a double is never stored, and the
+// neighbour words the slow path loads decode to the same nibbles before and after any store.
   constexpr int KK = D / 32;  // QK MFMAs per 16-token tile
   constexpr int MT = D / 16;  // PV M-tiles; V bytes per lane per token
   constexpr int KB = D / 4;   // K bytes per lane per token
@@ -57,6 +61,9 @@
   // the sequence's n_b rows: the tile's largest key limit unless the span overruns q_max
   const int64_t ctx = counts ? min<int64_t>(a.ctx_lens[b], a.ctx_cap) : cm.ctx;
   uint32_t n_single = 0, n_double = 0;
+#ifdef ATTN_BODY_REPAIR  // [repair] bytes rewritten: the statistics buffer's word 2
+  uint32_t n_rewritten = 0;
+#endif
 #else
   const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns
 #endif
@@ -165,7 +172,38 @@
     const float *ks = cur.ks, *vs = cur.vs;
     auto &kw = cur.kw;
     auto &vw = cur.vw;
-#ifdef ATTN_BODY_STATS  // [statistics] the stored words, before any is rewritten; rows past n_b are -1
+#ifdef ATTN_BODY_REPAIR  // [repair] the [statistics] island below, storing (as in attn_h84_mfma_body.inc):
+    // the stored words, before the slow path rewrites any in registers
+    if (counts) {
+#pragma unroll
+      for (int tau = 0; tau < 2; ++tau) {
+        const int32_t r = rows[kHalo + i0 + 16 * tau + n];
+        uint32_t dirty = 0;
+#pragma unroll
+        for (int k = 0; k < KW; ++k) dirty |= h_code4(kw[tau][k]);
+        if (r >= 0 && dirty) {
+          const uint32_t off = (uint32_t)r * (uint32_t)D + (uint32_t)(KB * g);  // load_step's
+#pragma unroll
+          for (int k = 0; k < KW; ++k) h84_repair_store(krs, off + 4u * k, kw[tau][k], n_single, n_double, n_rewritten);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        uint32_t dirty = 0;
+#pragma unroll
+        for (int k = 0; k < VW; ++k) dirty |= h_code4(vw[j][k] & kVMask);
+        if (rv[j] >= 0 && dirty) {
+          const uint32_t off = (uint32_t)rv[j] * (uint32_t)D + (uint32_t)(MT * n);
+          if constexpr (MT < 4) {  // head_dim 32: the lane's two bytes, as a two-byte store
+            h84_repair_store<2>(vrs, off, vw[j][0] & kVMask, n_single, n_double, n_rewritten);
+          } else {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) h84_repair_store(vrs, off + 4u * k, vw[j][k], n_single, n_double, n_rewritten);
+          }
+        }
+      }
+    }
+#elif defined(ATTN_BODY_STATS)  // [statistics] the stored words, before any is rewritten; rows past n_b are -1
     if (counts) {
 #pragma unroll
       for (int tau = 0; tau < 2; ++tau) {
@@ -337,7 +375,12 @@
   }
 #ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
   if (counts) {
+#ifdef ATTN_BODY_REPAIR  // [repair] ... and a third for the bytes rewritten
+    const uint32_t cnt[3] = {n_single, n_double, n_rewritten};
+    flush_stats_n<3>(a.stats, cnt);
+#else
     const uint32_t cnt[2] = {n_single, n_double};
     flush_stats_n<2>(a.stats, cnt);
+#endif
   }
 #endif

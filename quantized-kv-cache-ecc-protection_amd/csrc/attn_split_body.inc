@@ -10,6 +10,9 @@
 // define ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
 // So do the Golay counted kernels (paged_attn_split_golay_stats_kernel, `a` a StatsArgs, ATTN_BODY_CHUNK 1):
 // their counters hold bits corrected / uncorrectable words (Chunk::count) under the same names.
+// The repairing kernels (paged_attn_split_repair*_kernel, `a` a RepairArgs / RepairInterpArgs, Hamming(8,4))
+// define ATTN_BODY_REPAIR besides ATTN_BODY_STATS: the [repair] islands, in which the counting workgroup's
+// live lanes store the corrected codewords of the rows they count (kvecc.h "Repairing attention").
   constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
   using C = Chunk<CODEC, VEC>;
   constexpr int E = C::E;
@@ -68,6 +71,9 @@
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
   const int ntok_att = (int)max<int64_t>(min<int64_t>(ctx - t0, ntok), 0);
   uint32_t n_single = 0, n_double = 0;
+#ifdef ATTN_BODY_REPAIR  // [repair] bytes rewritten: the statistics buffer's word 2
+  uint32_t n_rewritten = 0;
+#endif
 #else
   const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
   const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
@@ -245,11 +251,26 @@
             n_single += f & 0x3Fu;  // bits corrected
             n_double += f >> 6;     // uncorrectable words
           } else {
+#ifdef ATTN_BODY_REPAIR  // [repair] count and store: the lane's words are whole words of its row (VEC divides the
+            // row's words), at load_buf's offsets.  A lane whose words are all clean codewords does neither.
+            uint32_t dirty = 0;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) dirty |= h_code4(kc[u].w[k]) | h_code4(vc[u].w[k]);
+            if (dirty) {
+              const uint32_t off = (uint32_t)rows[i0 + u * TP] * (uint32_t)a.d + 4u * VEC * c;
+#pragma unroll
+              for (int k = 0; k < VEC; ++k) {
+                h84_repair_store(krs, off + 4u * k, kc[u].w[k], n_single, n_double, n_rewritten);
+                h84_repair_store(vrs, off + 4u * k, vc[u].w[k], n_single, n_double, n_rewritten);
+              }
+            }
+#else
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
               h84_count4(kc[u].w[k], n_single, n_double);
               h84_count4(vc[u].w[k], n_single, n_double);
             }
+#endif
           }
         }
         ok[u] = ok[u] && i0 + u * TP < ntok_att;  // rows past the row's own key limit: counted, not attended
@@ -398,8 +419,13 @@
   }
 #ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
   if (counts) {
+#ifdef ATTN_BODY_REPAIR  // [repair] ... and a third for the bytes rewritten
+    const uint32_t cnt[3] = {n_single, n_double, n_rewritten};
+    flush_stats_n<3>(a.stats, cnt);
+#else
     const uint32_t cnt[2] = {n_single, n_double};
     flush_stats_n<2>(a.stats, cnt);
+#endif
   }
 #endif
   if (a.ctr) combine_if_last<T, G>(a, b * a.heads + h0, reinterpret_cast<float *>(rows));

@@ -461,6 +461,30 @@ KV_HD uint32_t h84_scrub4(uint32_t w, uint32_t &n_single, uint32_t &n_double, ui
   return x;
 }
 
+// h84_scrub4 without the decode / re-encode round trip, for the attention kernels
+// that repair in passing (attention.hip): the same XOR and the same three counts,
+// from h_code4 alone.  A correctable byte is one with an overall-parity error; its
+// wrong bit is the one whose H column is the syndrome (d0..d3 -> 3, 5, 6, 7; p0, p1,
+// p2 -> 1, 2, 4; P -> 0), so the XOR is that bit, and the bytes rewritten are the
+// bytes with a parity error.  (tests/native/h84_repair_check.cpp: equal to
+// h84_scrub4 for every byte value in every position.)
+constexpr uint64_t h_flip_table() {
+  constexpr uint32_t bit_of_syndrome[8] = {7, 4, 5, 0, 6, 1, 2, 3};
+  uint64_t t = 0;
+  for (uint32_t s = 0; s < 8; ++s) t |= (uint64_t)(1u << bit_of_syndrome[s]) << (8 * s);
+  return t;
+}
+constexpr uint64_t kHFlip = h_flip_table();
+KV_HD uint32_t h84_repair4(uint32_t w, uint32_t &n_single, uint32_t &n_double, uint32_t &n_rewritten) {
+  const uint32_t c = h_code4(w);  // syndrome in bits 0..2, parity error x 0xF0 in bits 4..7 of each byte
+  const uint32_t nz = ((c & 0x07070707u) + 0x07070707u) & 0x08080808u;
+  n_single += __builtin_popcount(nz & (c >> 1));
+  n_double += __builtin_popcount(nz & ~(c >> 1));
+  n_rewritten += __builtin_popcount(c & 0x10101010u);
+  const uint32_t pe = (c & 0xF0F0F0F0u) | ((c >> 4) & 0x0F0F0F0Fu);  // 0xFF per byte with a parity error
+  return byte_perm((uint32_t)(kHFlip >> 32), (uint32_t)kHFlip, c & 0x07070707u) & pe;
+}
+
 // four Hamming(7,4) codewords: any non-zero syndrome is "corrected" (doubles are
 // miscorrected, as the decoder does); bit 7 of each byte is not part of the code
 KV_HD uint32_t h74_scrub4(uint32_t w, uint32_t &n_flag, uint32_t &n_rewritten) {

@@ -1237,6 +1237,69 @@ KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batc
 // V byte of the first n_b positions of each sequence that has a valid query token -- once per
 // (sequence, cache head), whatever the query rows and heads that look at it.  stats is a host
 // buffer: the totals go to stats[0] / stats[1].
+// Repairing twin (kvecc_paged_attention_repair, `repair`): the same output -- computed first, on
+// the cache as it stood -- and the same counts, and h84_scrub4 over the same region: every counted
+// word with a correctable non-canonical byte is stored back, stats[2] += bytes rewritten.
+static int cpu_attention_stats_impl(const char *who, bool repair, const void *query, int64_t q_batch_stride,
+                                    int64_t q_token_stride, int64_t q_head_stride, int q_dtype, void *k_cache,
+                                    void *v_cache, const int32_t *block_table, const int32_t *context_lens,
+                                    const int32_t *q_spans, const float *k_scales, const float *v_scales,
+                                    void *out, int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                    int64_t head_dim, int64_t num_blocks, int64_t num_layers, int64_t layer,
+                                    int64_t block_size, int64_t max_blocks, int64_t max_context_len,
+                                    float sm_scale, int codec, int interp, uint64_t *stats, int threads) {
+  if (!stats) return set_error(KVECC_EINVAL, "%s: null stats", who);
+  if (codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "%s: codec %d (the %s twin needs hamming84)", who, codec,
+                     repair ? "repairing" : "counted");
+  if (q_max < 0) return set_error(KVECC_EINVAL, "%s: negative q_max", who);
+  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
+      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
+    return set_error(KVECC_EINVAL, "%s: bad query strides", who);
+  if (head_dim % 4 != 0) return set_error(KVECC_EINVAL, "%s: hamming84 head_dim must be a multiple of 4", who);
+  const int rc = cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                    block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads,
+                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                    max_context_len, sm_scale, codec, threads, q_spans, interp != 0);
+  if (rc != KVECC_OK || batch == 0 || heads == 0 || q_max == 0) return rc;
+  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
+  uint32_t n1 = 0, n2 = 0, nr = 0;
+  uint64_t c1 = 0, c2 = 0, cr = 0;
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_max;
+    if (first < 0 || count <= 0 || first >= q_max) continue;  // all padding: the sequence is not read
+    const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
+    for (int64_t pos = 0; pos < nb; ++pos) {
+      const int32_t blk = block_table[b * max_blocks + pos / block_size];
+      if (blk < 0) continue;
+      for (int64_t hk = 0; hk < kv_heads; ++hk) {
+        const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
+        for (void *cache : {k_cache, v_cache}) {
+          uint8_t *c = reinterpret_cast<uint8_t *>(cache) + srow * head_dim;
+          for (int64_t j = 0; j < head_dim; j += 4) {
+            const uint32_t w = load4(c + j);
+            if (repair) {
+              const uint32_t x = h84_scrub4(w, n1, n2, nr);
+              if (x) store4(c + j, w ^ x);
+            } else {
+              uint32_t d, t;
+              h84_decode4(w, d, t, n1, n2);
+            }
+          }
+        }
+        c1 += n1;
+        c2 += n2;
+        cr += nr;
+        n1 = n2 = nr = 0;
+      }
+    }
+  }
+  stats[0] += c1;
+  stats[1] += c2;
+  if (repair) stats[2] += cr;
+  return KVECC_OK;
+}
+
 KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch_stride,
                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                               const void *k_cache, const void *v_cache,
@@ -1248,48 +1311,29 @@ KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch
                                               int64_t layer, int64_t block_size, int64_t max_blocks,
                                               int64_t max_context_len, float sm_scale, int codec, int interp,
                                               uint64_t *stats, int threads) {
-  if (!stats) return set_error(KVECC_EINVAL, "cpu_paged_attention_stats: null stats");
-  if (codec != KVECC_CODEC_H84)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_stats: codec %d (the counted twin needs hamming84)", codec);
-  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_stats: negative q_max");
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_stats: bad query strides");
-  if (head_dim % 4 != 0)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_stats: hamming84 head_dim must be a multiple of 4");
-  const int rc = cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, threads, q_spans, interp != 0);
-  if (rc != KVECC_OK || batch == 0 || heads == 0 || q_max == 0) return rc;
-  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
-  uint32_t n1 = 0, n2 = 0;
-  uint64_t c1 = 0, c2 = 0;
-  for (int64_t b = 0; b < batch; ++b) {
-    const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_max;
-    if (first < 0 || count <= 0 || first >= q_max) continue;  // all padding: the sequence is not read
-    const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
-    for (int64_t pos = 0; pos < nb; ++pos) {
-      const int32_t blk = block_table[b * max_blocks + pos / block_size];
-      if (blk < 0) continue;
-      for (int64_t hk = 0; hk < kv_heads; ++hk) {
-        const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
-        for (const void *cache : {k_cache, v_cache}) {
-          const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * head_dim;
-          for (int64_t j = 0; j < head_dim; j += 4) {
-            uint32_t d, t;
-            h84_decode4(load4(c + j), d, t, n1, n2);
-          }
-        }
-        c1 += n1;
-        c2 += n2;
-        n1 = n2 = 0;
-      }
-    }
-  }
-  stats[0] += c1;
-  stats[1] += c2;
-  return KVECC_OK;
+  // (the caches are only read: `repair` false)
+  return cpu_attention_stats_impl("cpu_paged_attention_stats", false, query, q_batch_stride, q_token_stride,
+                                  q_head_stride, q_dtype, const_cast<void *>(k_cache), const_cast<void *>(v_cache),
+                                  block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                  kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                  max_context_len, sm_scale, codec, interp, stats, threads);
+}
+
+KVECC_API int kvecc_cpu_paged_attention_repair(const void *query, int64_t q_batch_stride,
+                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                               void *k_cache, void *v_cache, const int32_t *block_table,
+                                               const int32_t *context_lens, const int32_t *q_spans,
+                                               const float *k_scales, const float *v_scales, void *out,
+                                               int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                               int64_t layer, int64_t block_size, int64_t max_blocks,
+                                               int64_t max_context_len, float sm_scale, int codec, int interp,
+                                               uint64_t *stats, int threads) {
+  return cpu_attention_stats_impl("cpu_paged_attention_repair", true, query, q_batch_stride, q_token_stride,
+                                  q_head_stride, q_dtype, k_cache, v_cache, block_table, context_lens, q_spans,
+                                  k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim, num_blocks,
+                                  num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                                  interp, stats, threads);
 }
 
 // Golay counted twin (kvecc_paged_attention_golay_stats): the ragged twin's output (q_spans may be

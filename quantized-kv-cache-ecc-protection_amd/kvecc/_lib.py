@@ -82,6 +82,9 @@ SIGNATURES = {
     "kvecc_paged_attention_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                     _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int,
                                     _vp, _vp, _i64, _vp],
+    "kvecc_paged_attention_repair": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                     _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int,
+                                     _vp, _vp, _i64, _vp],
     "kvecc_paged_attention_golay_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                           _f32, _int, _vp, _vp, _i64, _vp],
@@ -132,6 +135,9 @@ SIGNATURES = {
     "kvecc_cpu_paged_attention_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                         _f32, _int, _int, _vp, _int],
+    "kvecc_cpu_paged_attention_repair": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                         _f32, _int, _int, _vp, _int],
     "kvecc_cpu_paged_attention_golay_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                               _i64, _f32, _int, _vp, _int],

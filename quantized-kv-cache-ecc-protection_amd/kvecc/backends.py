@@ -31,9 +31,10 @@ FUNCTIONS = (
 # (the shim then raises where it needs one): the in-place cache scrub, and the
 # paged attention entries (paged_attention_chunk_into takes interp=True: the
 # interpolating attention of ECCShimConfig(interp_attention=True);
-# paged_attention_counted_into: the counted attention of counted_attention=True).
+# paged_attention_counted_into: the counted attention of counted_attention=True;
+# paged_attention_repair_into: the repairing attention of repair_attention=True).
 NATIVE_FUNCTIONS = ("cache_scrub_tensors", "paged_attention_into", "paged_attention_chunk_into",
-                    "paged_attention_counted_into")
+                    "paged_attention_counted_into", "paged_attention_repair_into")
 
 # backend name -> module implementing FUNCTIONS
 CODEC_BACKENDS = {

@@ -636,9 +636,16 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
-                               interp=False, stats=None):
+                               interp=False, stats=None, repair=False):
     """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
     from .ops import _check_attention_chunk_args, _check_interp_codec, _check_q_spans, _check_stats_codec
+    if repair:
+        if stats is None:
+            raise ValueError("repair=True needs stats= (a host int64 buffer of >= 3 elements): the repairing "
+                             "twin counts")
+        return paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                           out, layer_idx, block_size, sm_scale, codec, stats,
+                                           max_context_len=max_context_len, q_spans=q_spans, interp=interp)
     _check_cpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
@@ -686,6 +693,39 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
               _ptr(context_lens), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads,
               head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
               int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
+    return out
+
+
+def paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, layer_idx, block_size, sm_scale, codec, stats, max_context_len=0,
+                                q_spans=None, interp=False):
+    """Host twin of ops.paged_attention_repair_into (kvecc_cpu_paged_attention_repair):
+    same arguments, checks and rules; k_cache / v_cache are written in place and
+    ``stats`` is a host int64 [>= 3] (new_scrub_stats): words 0 / 1 the counted
+    twin's, word 2 += bytes rewritten."""
+    from .ops import _check_attention_chunk_args, _check_q_spans, _check_repair_codec
+    _check_repair_codec(codec)
+    if stats is None:
+        raise ValueError("paged_attention_repair_into needs a stats buffer (cpu_ops.new_scrub_stats)")
+    _check_cpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
+            or stats.numel() < 3 or stats.device.type != "cpu"):
+        raise ValueError("stats must be a contiguous int64 host tensor of >= 3 elements (cpu_ops.new_scrub_stats), "
+                         f"got {getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
+                         f"on {getattr(stats, 'device', None)}")
+    batch, q_len, heads, head_dim = query.shape
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    max_blocks = block_table.shape[1]
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
+    _lib.call("kvecc_cpu_paged_attention_repair", _ptr(query), query.stride(0), query.stride(1),
+              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+              int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), _ptr(stats),
+              NUM_THREADS)
     return out
 
 

@@ -155,6 +155,18 @@ class ECCShimConfig:
     adds the bits corrected / uncorrectable words of the codewords it reads to
     the shim's statistics, exactly ``decode_stats=True``'s counts, with the same
     precedence, fall-back and held-span difference as ``stats_attention``.
+    ``repair_attention`` (append mode, hamming84 with or without
+    use_interpolation, opt-in) is ``stats_attention`` with read-repair: every
+    forward of ``_append_attend`` goes through kvecc_paged_attention_repair when
+    head_dim <= 256, which gives the counted call's outputs and counts and writes
+    the corrected codeword back over every single-error or parity-only byte it
+    reads -- the layer's resident cache comes out as scrub_ecc_cache(model,
+    layers=[layer]) would leave it, on every forward, with no separate pass to
+    schedule.  It takes ``stats_attention``'s place and precedence (and its
+    fall-back above head_dim 256, which repairs nothing); the bytes rewritten
+    accumulate in get_ecc_repaired(model).  A sequence held at count 0 is neither
+    read nor repaired, and the other codecs, layers that are not being read and
+    the scales still need the scrubber.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -166,7 +178,7 @@ class ECCShimConfig:
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
                  decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False,
-                 stats_attention=False, counted_attention=False):
+                 stats_attention=False, counted_attention=False, repair_attention=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -212,6 +224,10 @@ class ECCShimConfig:
             raise ValueError("counted_attention=True needs cache_mode='append' and codec 'hamming84' or 'golay', "
                              f"not codec={codec!r}, cache_mode={cache_mode!r}")
         self.counted_attention = bool(counted_attention)
+        if repair_attention and (cache_mode != "append" or codec != "hamming84"):
+            raise ValueError("repair_attention=True needs cache_mode='append' and codec='hamming84', "
+                             f"not codec={codec!r}, cache_mode={cache_mode!r}")
+        self.repair_attention = bool(repair_attention)
 
 
 class SimpleBlockManager:
@@ -420,6 +436,12 @@ class ECCBackend:
         self._injection_count = 0
         self._total_values = 0
         self._stats = self.codec_backend.new_stats(manager.k_cache.device)  # backend counters
+        if getattr(config, "repair_attention", False):
+            # the repairing attention adds the bytes it rewrites to word 2, which no other
+            # writer of this buffer touches: a buffer with that word on every backend
+            if not hasattr(self.codec_backend, "paged_attention_repair_into"):
+                raise ValueError("repair_attention=True needs a backend with paged_attention_repair_into")
+            self._stats = self.codec_backend.new_scrub_stats(manager.k_cache.device)
         # cumulative counters of scrub() alone (corrected, detected, rewritten,
         # scanned), allocated by the first scrub; get_ecc_stats never reads them
         self._scrub_stats = None
@@ -710,6 +732,25 @@ class ECCBackend:
             self.codec_backend.paged_attention_counted_into(
                 qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, self._stats, max_context_len=ctx, q_spans=sp)
+            return out.transpose(1, 2)
+        if cfg.repair_attention and d <= 256:
+            # the counted route below on the repairing kernels: the same outputs and counts, and
+            # the correctable bytes read are rewritten in mgr.k_cache / mgr.v_cache in place
+            sp = None
+            if self._spans is not None:
+                self._check_spans(b, q_len)
+                sp = self._span_buf[:b]
+            qt = q.transpose(1, 2)
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention_repair(
+                    qt, mgr.k_cache, mgr.v_cache, table, dev_lens, sp, mgr.k_scales, mgr.v_scales, self._stats,
+                    layer_idx, mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, interp, ctx)
+                return out.transpose(1, 2)
+            out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+            self.codec_backend.paged_attention_repair_into(
+                qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, self._stats, max_context_len=ctx, q_spans=sp,
+                interp=interp)
             return out.transpose(1, 2)
         if (cfg.stats_attention or cfg.counted_attention) and d <= 256:  # (counted_attention: hamming84 here)
             # every q_len on the counted kernels: q read in place as [batch, q_len,
@@ -1236,6 +1277,20 @@ def get_ecc_stats(model):
         stats["errors_detected"] = detected
         stats["total_values"] = be._total_values
     return stats
+
+
+def get_ecc_repaired(model):
+    """Bytes the repairing attention (ECCShimConfig(repair_attention=True)) has
+    rewritten in the resident cache since the last reset_ecc_cache: the sum of
+    what a scrub of each layer before each forward would have reported as
+    "rewritten".  One device sync; 0 without the flag.  get_ecc_stats does not
+    include it."""
+    if not hasattr(model, "_ecc_backend"):
+        raise ValueError("model is not patched with patch_model_with_ecc_attention")
+    be = model._ecc_backend
+    if not getattr(be.config, "repair_attention", False):
+        return 0
+    return be.codec_backend.read_stats(be._stats, 3)[2]
 
 
 _SCRUB_KEYS = ("corrected", "detected", "rewritten", "scanned")

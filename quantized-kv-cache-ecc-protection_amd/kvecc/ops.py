@@ -1240,7 +1240,7 @@ def _check_stats_codec(codec):
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
-                               interp=False, stats=None):
+                               interp=False, stats=None, repair=False):
     """kvecc_paged_attention_chunk: q_len query tokens per sequence, causal (include/kvecc.h).
 
     query [B, q_len, H, D] with any strides and a unit innermost one (the
@@ -1265,7 +1265,19 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     SINGLE_CORRECTED / DOUBLE_DETECTED classification of every stored K and V byte
     of each sequence that has a valid token to stats[0] / stats[1], exactly once,
     as shim_read(ctx = n_b, stats) counts them; with or without interp and
-    q_spans, q_len 1 included."""
+    q_spans, q_len 1 included.
+
+    repair=True (needs stats; hamming84 only; kvecc_paged_attention_repair):
+    the counted call's output and counts, and k_cache / v_cache are MUTATED in
+    place -- every correctable non-canonical byte the call counts is rewritten
+    as cache_scrub_tensors would, stats[2] += bytes rewritten
+    (paged_attention_repair_into)."""
+    if repair:
+        if stats is None:
+            raise ValueError("repair=True needs stats= (an ops.new_stats buffer): the repairing kernels count")
+        return paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                           out, layer_idx, block_size, sm_scale, codec, stats,
+                                           max_context_len=max_context_len, q_spans=q_spans, interp=interp)
     _check_gpu(query, "Query")
     _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                 out, block_size, codec)
@@ -1315,11 +1327,13 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
 
 def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                           layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0,
-                          q_spans=None, interp=False, stats=None):
+                          q_spans=None, interp=False, stats=None, repair=False):
     """paged_attention_chunk_into with a fresh [B, q_len, H, D] output; on the
     GPU or, for host tensors, through the host twin.  q_spans: a ragged call;
     interp: double errors interpolated (hamming84); stats: the counted kernels
-    (hamming84), decode statistics added to the buffer."""
+    (hamming84), decode statistics added to the buffer; repair (with stats):
+    the repairing kernels, which also rewrite the correctable bytes they count
+    in k_cache / v_cache."""
     if sm_scale is None:
         sm_scale = 1.0 / math.sqrt(query.shape[-1])
     out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
@@ -1328,11 +1342,52 @@ def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_
         return cpu_ops.paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
                                                   v_scales, out, layer_idx, block_size, sm_scale, codec,
                                                   max_context_len=max_context_len, q_spans=q_spans,
-                                                  interp=interp, stats=stats)
+                                                  interp=interp, stats=stats, repair=repair)
     return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                       out, layer_idx, block_size, sm_scale, codec,
                                       max_context_len=max_context_len, q_spans=q_spans, interp=interp,
-                                      stats=stats)
+                                      stats=stats, repair=repair)
+
+
+def _check_repair_codec(codec):
+    if codec != "hamming84":
+        raise ValueError(f"repair needs hamming84 (the repairing attention kernels), got codec {codec!r}")
+
+
+def paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, layer_idx, block_size, sm_scale, codec, stats, max_context_len=0,
+                                q_spans=None, interp=False):
+    """kvecc_paged_attention_repair (include/kvecc.h "Repairing attention"):
+    paged_attention_chunk_into(stats=...)'s output and counts over a hamming84
+    cache, and read-repair: k_cache and v_cache are written in place.  Every
+    stored byte the call counts -- layer layer_idx, the first n_b positions of
+    each sequence with a valid token -- that is a single (type 1) or
+    parity-only (type 3) codeword becomes encode(decoded data), exactly what
+    cache_scrub_tensors leaves there; doubles, clean bytes and every other byte
+    of the caches keep their bits.  stats[2] += bytes rewritten
+    (read_stats(stats, 3))."""
+    _check_repair_codec(codec)
+    if stats is None:
+        raise ValueError("paged_attention_repair_into needs a stats buffer (ops.new_stats)")
+    _check_gpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    sp = _sptr(stats, query.device)
+    batch, q_len, heads, head_dim = query.shape
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    max_blocks = block_table.shape[1]
+    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
+    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
+    ws = _attn_workspace(query.device, ws_n)
+    _lib.call("kvecc_paged_attention_repair", _ptr(query), query.stride(0), query.stride(1),
+              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
+              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
+              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
+              mcl, float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), sp, _ptr(ws), ws.numel(),
+              _stream(query.device))
+    return out
 
 
 _GOLAY_CODECS = ("golay", "golay_packed")

@@ -481,11 +481,34 @@ def _(query, k_cache, v_cache, block_table, context_lens, q_spans, k_scales, v_s
     return query.new_empty(query.shape)
 
 
+@torch.library.custom_op("kvecc::paged_attention_repair", mutates_args=("k_cache", "v_cache", "stats"),
+                         device_types=_DEV)
+def paged_attention_repair(query: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor,
+                           context_lens: Tensor, q_spans: Optional[Tensor], k_scales: Tensor, v_scales: Tensor,
+                           stats: Tensor, layer_idx: int, block_size: int, sm_scale: float, codec: str,
+                           interp: bool = False, max_context_len: int = 0) -> Tensor:
+    """Repairing paged attention over a Hamming(8,4) cache (kvecc_paged_attention_repair):
+    paged_attention_stats's output and counts, and every correctable non-canonical
+    byte it counts rewritten in `k_cache` / `v_cache` in place as cache_scrub would
+    (stats word 2 += bytes rewritten); q_spans None: a uniform call."""
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    _be(query).paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
+                                           v_scales, out, layer_idx, block_size, sm_scale, codec, stats,
+                                           max_context_len=max_context_len, q_spans=q_spans, interp=interp)
+    return out
+
+
+@paged_attention_repair.register_fake
+def _(query, k_cache, v_cache, block_table, context_lens, q_spans, k_scales, v_scales, stats, layer_idx,
+      block_size, sm_scale, codec, interp=False, max_context_len=0):
+    return query.new_empty(query.shape)
+
+
 OPS: List[str] = ["hamming74_encode", "hamming84_encode", "hamming74_decode", "hamming84_decode",
                   "golay_encode", "golay_decode", "golay_encode_rows", "golay_decode_rows",
                   "inject_bit_errors", "inject_bit_errors_", "interpolate_double_errors",
                   "fused_quantize_encode", "fused_decode_dequantize_hamming84", "shim_write", "shim_append",
                   "shim_append_ragged", "shim_read", "cache_scrub", "paged_attention", "paged_attention_chunk",
                   "paged_attention_chunk_ragged", "paged_attention_interp", "paged_attention_stats",
-                  "paged_attention_golay_stats"]
+                  "paged_attention_golay_stats", "paged_attention_repair"]
 _ = _lib  # the operators bind libkvecc.so lazily, on first call

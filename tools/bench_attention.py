@@ -41,6 +41,15 @@ interp 0 and 1, the uncounted plain (decode / chunk) and interpolating entries o
 and shim_read_batch(stats=...) + repeat_interleave + masked SDPA, the path
 ECCShimConfig(stats_attention=True) replaces (with and without interpolation).
 
+--repair times the repairing entry (kvecc_paged_attention_repair, Hamming(8,4)) in one process at
+--kv-heads and --heads / 4 cache heads, q_len 1 and 16, plain and interpolating, one JSON line per
+case, every pass visiting the variants in turn.  Clean cache: the repairing call against the
+counted call, --iters calls between one event pair.  Dirty cache (BER 1e-3 in every bit): the
+repairing call against the counted call plus a one-layer cache_scrub launch on the same cache --
+the pair it replaces -- with the dirty cache restored by a device copy before EVERY timed call,
+outside that call's event pair (the repairing call cleans what it reads); and the second, now
+clean, repairing call.
+
 --pkg DIR imports kvecc from DIR instead of this tree (the same measurement on
 another build, e.g. the parent commit's, in the same session).
 """
@@ -99,6 +108,8 @@ def main():
                     help="the byte family (int4, hamming74) beside hamming84, alternated in one process")
     ap.add_argument("--stats", action="store_true",
                     help="the counted entry beside the uncounted kernels and the counting read + SDPA")
+    ap.add_argument("--repair", action="store_true",
+                    help="the repairing entry beside the counted entry and the counted entry + cache_scrub")
     ap.add_argument("--pkg", default=None, help="directory to import kvecc from (default: this tree)")
     args = ap.parse_args()
     if args.pkg:
@@ -109,6 +120,8 @@ def main():
         return bench_interp(args, ops, dev)
     if args.bytes:
         return bench_bytes(args, ops, dev)
+    if args.repair:
+        return bench_repair(args, ops, dev)
     if args.stats:
         return bench_stats(args, ops, dev)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -544,6 +557,133 @@ def bench_stats(args, ops, dev):
                                   "block_size": args.bs, "ber": ber, "counts_per_call": totals, **res}), flush=True)
             del kc, vc
         del x
+
+
+def bench_repair(args, ops, dev):
+    import statistics
+    import time
+
+    from kvecc.memory_layout import kv_cache_pair
+    if args.codec != "hamming84":
+        raise SystemExit("--repair needs --codec hamming84")
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    sm = 1 / math.sqrt(args.d)
+
+    def summary(passes):
+        return {name: {"us_per_call": round(statistics.median(p), 2), "pass_us": [round(x, 2) for x in p],
+                       "spread_us": round(max(p) - min(p), 2)} for name, p in passes.items()}
+
+    def warm(fn):
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 >= args.warmup_s:
+                break
+
+    def timed_alternating(cases):
+        """Every case warmed up, then --passes rounds that visit the cases in turn."""
+        for fn in cases.values():
+            warm(fn)
+        passes = {name: [] for name in cases}
+        for _ in range(args.passes):
+            for name, fn in cases.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                passes[name].append(e0.elapsed_time(e1) / args.iters * 1e3)
+        return summary(passes)
+
+    def timed_each(cases, iters):
+        """cases: name -> (prepare, fn).  prepare() runs before every timed call, outside its event
+        pair; a pass is the mean of `iters` single-call event pairs."""
+        for prep, fn in cases.values():
+            warm(lambda: (prep(), fn()))
+        passes = {name: [] for name in cases}
+        for _ in range(args.passes):
+            for name, (prep, fn) in cases.items():
+                evs = []
+                for _ in range(iters):
+                    prep()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    evs.append((e0, e1))
+                torch.cuda.synchronize()
+                passes[name].append(sum(a.elapsed_time(b) for a, b in evs) / iters * 1e3)
+        return summary(passes)
+
+    for kvh in (args.kv_heads, max(1, args.heads // 4)):
+        x = torch.randint(0, 16, (2, blocks, 1, kvh, args.bs, args.d), device=dev, generator=g, dtype=torch.uint8)
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        kc, vc = kv_cache_pair((blocks, 1, kvh, args.bs * args.d), torch.uint8, dev)
+        clean = [ops.hamming84_encode(x[side].reshape(-1)) for side in range(2)]
+        dirty = [c.clone() for c in clean]
+        for side, c in enumerate(dirty):
+            ops.inject_into(c, c, 1e-3, 8, seed=42 + side)
+
+        def restore(src):
+            def fn():
+                kc.view(-1).copy_(src[0])
+                vc.view(-1).copy_(src[1])
+            return fn
+
+        for n in (1, 16):
+            qc = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half()
+            qt = qc.transpose(1, 2)
+            outc = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+            stats, sstats = ops.new_stats(dev), ops.new_scrub_stats(dev)
+
+            def attend(interp, repair):
+                return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outc, 0, args.bs, sm,
+                                                              "hamming84", args.ctx, interp=interp, stats=stats,
+                                                              repair=repair)
+
+            def scrub():
+                ops.cache_scrub_tensors(kc, vc, table, lens, args.d, args.bs, 1, "hamming84", 0, 1, args.ctx, sstats)
+
+            for interp in (False, True):
+                # one repairing call against the counted call + scrub on the same dirty cache: the same
+                # output bits, counts and cache bytes
+                restore(dirty)()
+                stats.zero_()
+                sstats.zero_()
+                attend(interp, False)()
+                want_out, want = outc.clone(), ops.read_stats(stats)
+                scrub()
+                want_k, want_v, rewritten = kc.clone(), vc.clone(), ops.read_stats(sstats, 3)[2]
+                restore(dirty)()
+                stats.zero_()
+                attend(interp, True)()
+                got = ops.read_stats(stats, 3)
+                assert got == want + [rewritten], (got, want, rewritten)
+                assert torch.equal(outc.view(torch.int16), want_out.view(torch.int16))
+                assert torch.equal(kc, want_k) and torch.equal(vc, want_v)
+                restore(clean)()
+                res = {"clean": timed_alternating({"repair": attend(interp, True), "counted": attend(interp, False)})}
+                counted = attend(interp, False)
+                repair = attend(interp, True)
+                res["dirty"] = timed_each({
+                    "repair": (restore(dirty), repair),
+                    "counted_plus_scrub": (restore(dirty), lambda: (counted(), scrub())),
+                    "counted": (restore(dirty), counted),
+                    "repair_second_call": (lambda: (restore(dirty)(), repair()), repair),
+                }, max(1, args.iters // 4))
+                print(json.dumps({"kernel": "paged_attention_repair", "batch": args.batch, "q_len": n,
+                                  "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
+                                  "block_size": args.bs, "interp": interp, "dirty_ber": 1e-3,
+                                  "dirty_counts_per_call": got, **res}), flush=True)
+        del kc, vc, x, clean, dirty
 
 
 def bench_golay_stats(args, ops, dev):
