@@ -1088,6 +1088,17 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_stats_kernel(
 #undef ATTN_BODY_CHUNK
 }
 
+// ---- host side: one dispatch path ------------------------------------------------
+// Which kernel and which argument block serve a call of a given mode, codec,
+// head_dim, dtype and addressing is decided in this section, each decision once:
+//   with_q_dtype / with_head_dim / with_codec   run-time value -> template argument
+//   split_kernel / tile_kernel / decode_mfma_kernel   (block, codec, ...) -> kernel; a
+//     combination without a kernel does not compile, or where it is instantiated
+//     returns KVECC_EINVAL: nothing returns KVECC_OK having launched nothing
+//   launch_attn / launch_rows / launch_tiles / launch_decode_mfma   grid, launch, combine
+//   attn_setup   validation and argument fill of every entry
+// and `entry` is the C entry's name without "kvecc_", the prefix of its messages.
+
 template <typename T>
 static void launch_combine(const AttnArgs &a, int64_t batch, hipStream_t st) {
   if (a.nsplit <= kCombineWaveSplits && a.d <= 2 * kWave)
@@ -1102,44 +1113,97 @@ static int pow2_at_least(int64_t x) {
   return w;
 }
 
-// the split kernel of the argument type: the decode entry's (AttnArgs) or the
-// chunked call's over its virtual batch (ChunkArgs)
-#define KVECC_SPLIT_LAUNCH(VEC_, WW, BUF_, G_)                                                                  \
-  do {                                                                                                          \
-    if constexpr (is_byte<A>) {                                                                                 \
-      if constexpr (CODEC == KVECC_CODEC_H84 && is_chunk<A>)                                                    \
-        KVECC_LAUNCH((paged_attn_split_byte_chunk_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
-      else if constexpr (CODEC == KVECC_CODEC_H84)                                                              \
-        KVECC_LAUNCH((paged_attn_split_byte_kernel<T, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
-    } else if constexpr (is_repair<A>) {                                                                        \
-      if constexpr (CODEC == KVECC_CODEC_H84 && BUF_ && std::is_same<A, RepairInterpArgs>::value)               \
-        KVECC_LAUNCH((paged_attn_split_repair_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);   \
-      else if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                      \
-        KVECC_LAUNCH((paged_attn_split_repair_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
-    } else if constexpr (is_stats<A>) {                                                                         \
-      if constexpr (CODEC == KVECC_CODEC_H84 && BUF_ && std::is_same<A, StatsInterpArgs>::value)                \
-        KVECC_LAUNCH((paged_attn_split_stats_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);    \
-      else if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                      \
-        KVECC_LAUNCH((paged_attn_split_stats_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);           \
-      else if constexpr (is_golay(CODEC) && BUF_ && std::is_same<A, StatsArgs>::value)                          \
-        KVECC_LAUNCH((paged_attn_split_golay_stats_kernel<T, CODEC, VEC_, WW, G_>), grid, dim3(kBlock), 0, st,  \
-                     a);                                                                                        \
-    } else if constexpr (is_interp<A>) {                                                                       \
-      if constexpr (CODEC == KVECC_CODEC_H84 && BUF_)                                                           \
-        KVECC_LAUNCH((paged_attn_split_interp_kernel<T, VEC_, WW, G_>), grid, dim3(kBlock), 0, st, a);          \
-    } else if constexpr (is_chunk<A>)                                                                           \
-      KVECC_LAUNCH((paged_attn_split_chunk_kernel<T, CODEC, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a); \
-    else                                                                                                        \
-      KVECC_LAUNCH((paged_attn_split_kernel<T, CODEC, VEC_, WW, BUF_, G_>), grid, dim3(kBlock), 0, st, a);      \
-  } while (0)
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+template <int V>
+using int_tag = std::integral_constant<int, V>;
+
+// f(type_tag<T>) for the query's element type T
+template <typename F>
+static int with_q_dtype(const char *entry, int q_dtype, F &&f) {
+  switch (q_dtype) {
+    case KVECC_F32: return f(type_tag<float>{});
+    case KVECC_F16: return f(type_tag<__half>{});
+    case KVECC_BF16: return f(type_tag<__hip_bfloat16>{});
+    default: return set_error(KVECC_EINVAL, "%s: bad dtype %d", entry, q_dtype);
+  }
+}
+
+// f(int_tag<D>) for a matrix-core kernel's head_dim: 32, 64 or 128 (attn_mfma_heads,
+// attn_chunk_mfma_heads)
+template <typename F>
+static int with_head_dim(int64_t d, F &&f) {
+  switch (d) {
+    case 32: return f(int_tag<32>{});
+    case 64: return f(int_tag<64>{});
+    default: return f(int_tag<128>{});
+  }
+}
+
+// The blocks whose kernels decode Golay caches too: every other block's decode
+// Hamming(8,4)'s layout only
+template <typename A>
+constexpr bool takes_golay = std::is_same<A, AttnArgs>::value || std::is_same<A, ChunkArgs>::value ||
+                             std::is_same<A, RaggedArgs>::value || std::is_same<A, StatsArgs>::value;
+// The blocks whose kernels address the caches through buffer descriptors only (caches under 4 GiB)
+template <typename A>
+constexpr bool buf_only = is_interp<A> || is_stats<A> || is_repair<A>;
+
+// f(int_tag<CODEC>) for the codec of block A's kernels (the byte family arrives as Hamming(8,4))
+template <typename A, typename F>
+static int with_codec(const char *entry, int codec, F &&f) {
+  if (codec == KVECC_CODEC_H84) return f(int_tag<KVECC_CODEC_H84>{});
+  if constexpr (takes_golay<A>) {
+    if (codec == KVECC_CODEC_GOLAY) return f(int_tag<KVECC_CODEC_GOLAY>{});
+    if (codec == KVECC_CODEC_GOLAY_PACKED) return f(int_tag<KVECC_CODEC_GOLAY_PACKED>{});
+  }
+  return set_error(KVECC_EINVAL, "%s: no kernel of this call's mode decodes codec %d", entry, codec);
+}
+
+// The split kernel of an argument block: the decode entry's (AttnArgs), the chunked
+// call's over its virtual batch (RaggedArgs), or a mode's own
+template <typename T, int CODEC, int VEC, int W, bool BUF, int G, typename A>
+constexpr auto split_kernel() {
+  if constexpr (std::is_same<A, AttnArgs>::value) {
+    return &paged_attn_split_kernel<T, CODEC, VEC, W, BUF, G>;
+  } else if constexpr (std::is_same<A, RaggedArgs>::value) {
+    return &paged_attn_split_chunk_kernel<T, CODEC, VEC, W, BUF, G>;
+  } else if constexpr (std::is_same<A, StatsArgs>::value && is_golay(CODEC)) {
+    static_assert(BUF, "the counted kernels are buffer-addressed");
+    return &paged_attn_split_golay_stats_kernel<T, CODEC, VEC, W, G>;
+  } else {
+    static_assert(CODEC == KVECC_CODEC_H84, "this block's kernels decode Hamming(8,4)'s layout only");
+    if constexpr (std::is_same<A, ByteAttnArgs>::value) {
+      return &paged_attn_split_byte_kernel<T, VEC, W, BUF, G>;
+    } else if constexpr (std::is_same<A, ByteChunkArgs>::value) {
+      return &paged_attn_split_byte_chunk_kernel<T, VEC, W, BUF, G>;
+    } else {
+      static_assert(BUF, "the interpolating, counted and repairing kernels are buffer-addressed");
+      if constexpr (std::is_same<A, InterpArgs>::value) {
+        return &paged_attn_split_interp_kernel<T, VEC, W, G>;
+      } else if constexpr (std::is_same<A, StatsArgs>::value) {
+        return &paged_attn_split_stats_kernel<T, VEC, W, G>;
+      } else if constexpr (std::is_same<A, StatsInterpArgs>::value) {
+        return &paged_attn_split_stats_interp_kernel<T, VEC, W, G>;
+      } else if constexpr (std::is_same<A, RepairArgs>::value) {
+        return &paged_attn_split_repair_kernel<T, VEC, W, G>;
+      } else {
+        static_assert(std::is_same<A, RepairInterpArgs>::value, "no split kernel takes this block");
+        return &paged_attn_split_repair_interp_kernel<T, VEC, W, G>;
+      }
+    }
+  }
+}
 
 template <typename T, int CODEC, int VEC, bool BUF, typename A>
 static int launch_split_w(const A &a, dim3 grid, hipStream_t st) {
   const int w = pow2_at_least((a.g + VEC - 1) / VEC);
   switch (w) {
-#define KVECC_ATTN_CASE(WW)                \
-  case WW:                                 \
-    KVECC_SPLIT_LAUNCH(VEC, WW, BUF, 1);   \
+#define KVECC_ATTN_CASE(WW)                                                                     \
+  case WW:                                                                                      \
+    KVECC_LAUNCH((split_kernel<T, CODEC, VEC, WW, BUF, 1, A>()), grid, dim3(kBlock), 0, st, a); \
     return KVECC_OK;
     KVECC_ATTN_CASE(1)
     KVECC_ATTN_CASE(2)
@@ -1156,9 +1220,12 @@ static int launch_split_w(const A &a, dim3 grid, hipStream_t st) {
 }
 
 template <typename T, int CODEC, int VEC, typename A>
-static int launch_split(const A &a, dim3 grid, hipStream_t st) {
-  return a.cache_bytes ? launch_split_w<T, CODEC, VEC, true>(a, grid, st)
-                       : launch_split_w<T, CODEC, VEC, false>(a, grid, st);
+static int launch_split(const char *entry, const A &a, dim3 grid, hipStream_t st) {
+  if (a.cache_bytes) return launch_split_w<T, CODEC, VEC, true>(a, grid, st);
+  if constexpr (buf_only<A>)
+    return set_error(KVECC_EINVAL, "%s: no kernel of this call's mode reads caches of 4 GiB or more", entry);
+  else
+    return launch_split_w<T, CODEC, VEC, false>(a, grid, st);
 }
 
 // words per lane of a token row: the VEC the codec's kernels use at head_dim d
@@ -1183,100 +1250,112 @@ static int attn_heads_per_wg(int codec, int64_t d, int64_t g, int64_t heads, int
   return group % 4 == 0 && gmax >= 4 ? 4 : group % 2 == 0 ? 2 : 1;
 }
 
+// (gq > 1 only with buffer addressing: attn_heads_per_wg)
 template <typename T, int CODEC, int VEC, int G, typename A>
 static int launch_split_gqa(const A &a, dim3 grid, hipStream_t st) {
   switch (pow2_at_least((a.g + VEC - 1) / VEC)) {
-    case 8: KVECC_SPLIT_LAUNCH(VEC, 8, true, G); break;
-    case 16: KVECC_SPLIT_LAUNCH(VEC, 16, true, G); break;
-    default: KVECC_SPLIT_LAUNCH(VEC, 32, true, G); break;
+    case 8: KVECC_LAUNCH((split_kernel<T, CODEC, VEC, 8, true, G, A>()), grid, dim3(kBlock), 0, st, a); break;
+    case 16: KVECC_LAUNCH((split_kernel<T, CODEC, VEC, 16, true, G, A>()), grid, dim3(kBlock), 0, st, a); break;
+    default: KVECC_LAUNCH((split_kernel<T, CODEC, VEC, 32, true, G, A>()), grid, dim3(kBlock), 0, st, a); break;
   }
   return KVECC_OK;
 }
 
 template <typename T, int CODEC, int VEC, typename A>
-static int launch_split_g(const A &a, int64_t batch, int gq, hipStream_t st) {
+static int launch_split_g(const char *entry, const A &a, int64_t batch, int gq, hipStream_t st) {
   dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gq));
-  if (gq == 1) return launch_split<T, CODEC, VEC>(a, grid, st);
+  if (gq == 1) return launch_split<T, CODEC, VEC>(entry, a, grid, st);
   constexpr int GV = CODEC == KVECC_CODEC_H84 ? kH84GqaVec : VEC;
   if constexpr (CODEC != KVECC_CODEC_GOLAY_PACKED)
     if (gq == 4) return launch_split_gqa<T, CODEC, GV, 4>(a, grid, st);
   return launch_split_gqa<T, CODEC, GV, 2>(a, grid, st);
 }
 
+// The split kernels over `batch` query rows per head, then the combine unless it is
+// fused (a.ctr) or the caller's (combine false: launch_rows' slices)
 template <typename T, int CODEC, typename A>
-static int launch_attn(const A &a, int64_t batch, int gq, hipStream_t st, bool combine = true) {
+static int launch_attn(const char *entry, const A &a, int64_t batch, int gq, hipStream_t st, bool combine = true) {
   int rc;
   if constexpr (CODEC == KVECC_CODEC_H84) {
     if (a.d % (4 * kH84Vec) == 0)
-      rc = launch_split_g<T, CODEC, kH84Vec>(a, batch, gq, st);  // 16-byte loads, 16 codewords per lane
+      rc = launch_split_g<T, CODEC, kH84Vec>(entry, a, batch, gq, st);  // 16-byte loads, 16 codewords per lane
     else if (a.d % 16 == 0)
-      rc = launch_split_g<T, CODEC, 4>(a, batch, gq, st);
+      rc = launch_split_g<T, CODEC, 4>(entry, a, batch, gq, st);
     else
-      rc = launch_split_g<T, CODEC, 1>(a, batch, gq, st);
+      rc = launch_split_g<T, CODEC, 1>(entry, a, batch, gq, st);
   } else if constexpr (CODEC == KVECC_CODEC_GOLAY) {
-    rc = launch_split_g<T, CODEC, kGolayVec>(a, batch, gq, st);  // 3 codewords per lane: 43 -> 15 of 16 lanes
+    rc = launch_split_g<T, CODEC, kGolayVec>(entry, a, batch, gq, st);  // 3 codewords per lane: 43 -> 15 of 16 lanes
   } else {
-    rc = launch_split_g<T, CODEC, kGolayPackedVec>(a, batch, gq, st);  // 3 codewords per lane: 43 -> 15 of 16
+    rc = launch_split_g<T, CODEC, kGolayPackedVec>(entry, a, batch, gq, st);  // 3 codewords per lane: 43 -> 15 of 16
   }
   if (rc != KVECC_OK) return rc;
   if (!a.ctr && combine) launch_combine<T>(a, batch, st);
   return KVECC_OK;
 }
 
-// (A: AttnArgs, or ByteAttnArgs for the byte family's kernels)
-template <int D, typename A>
-static int launch_mfma_d(const A &a, int64_t batch, int gm, hipStream_t st) {
-  const dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gm));
-#define KVECC_MFMA_LAUNCH(G_)                                                                \
-  do {                                                                                       \
-    if constexpr (is_byte<A>)                                                                \
-      KVECC_LAUNCH((paged_attn_byte_mfma_kernel<D, G_>), grid, dim3(kBlock), 0, st, a);      \
-    else                                                                                     \
-      KVECC_LAUNCH((paged_attn_h84_mfma_kernel<D, G_>), grid, dim3(kBlock), 0, st, a);       \
-  } while (0)
-  switch (gm) {
-    case 1: KVECC_MFMA_LAUNCH(1); break;
-    case 2: KVECC_MFMA_LAUNCH(2); break;
-    case 4: KVECC_MFMA_LAUNCH(4); break;
-    case 8: KVECC_MFMA_LAUNCH(8); break;
-    default: KVECC_MFMA_LAUNCH(16); break;
-  }
-#undef KVECC_MFMA_LAUNCH
-  if (!a.ctr) launch_combine<__half>(a, batch, st);
-  return KVECC_OK;
+// The general path of a chunked call: the split kernels of block A over the virtual
+// batch of `rows` = batch * q_len query rows (ChunkArgs::q_len), in slices that fit
+// grid.y, then one combine over all rows.
+constexpr int64_t kMaxGridY = 65535;
+template <typename T, typename A>
+static int launch_rows(const char *entry, int codec, A a, int64_t rows, int gq, hipStream_t st) {
+  return with_codec<A>(entry, codec, [&](auto c) {
+    constexpr int CODEC = decltype(c)::value;
+    const int64_t wg_per_row = a.heads / gq;
+    if (rows * wg_per_row <= kMaxGridY) return launch_attn<T, CODEC>(entry, a, rows, gq, st);
+    const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
+    for (int64_t vb = 0; vb < rows; vb += per) {
+      a.vb0 = (uint32_t)vb;
+      const int rc = launch_attn<T, CODEC>(entry, a, std::min(per, rows - vb), gq, st, false);
+      if (rc != KVECC_OK) return rc;
+    }
+    launch_combine<T>(a, rows, st);
+    return (int)KVECC_OK;
+  });
 }
 
-template <bool PACKED>
-static int launch_golay_mfma(const AttnArgs &a, int64_t batch, int gm, hipStream_t st) {
-  const dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gm));
-  switch (gm) {
-    case 2: KVECC_LAUNCH((paged_attn_golay_mfma_kernel<2, PACKED>), grid, dim3(kBlock), 0, st, a); break;
-    case 4: KVECC_LAUNCH((paged_attn_golay_mfma_kernel<4, PACKED>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: KVECC_LAUNCH((paged_attn_golay_mfma_kernel<8, PACKED>), grid, dim3(kBlock), 0, st, a); break;
-    default: KVECC_LAUNCH((paged_attn_golay_mfma_kernel<16, PACKED>), grid, dim3(kBlock), 0, st, a); break;
+// The decode entry's matrix-core kernel of (block, codec, head_dim, G query heads per
+// workgroup); Golay: head_dim 128 and G >= 2 (attn_mfma_heads)
+template <typename A, int CODEC, int D, int G>
+constexpr auto decode_mfma_kernel() {
+  if constexpr (std::is_same<A, ByteAttnArgs>::value) {
+    static_assert(CODEC == KVECC_CODEC_H84, "the byte family decodes Hamming(8,4)'s layout");
+    return &paged_attn_byte_mfma_kernel<D, G>;
+  } else {
+    static_assert(std::is_same<A, AttnArgs>::value, "no decode matrix-core kernel takes this block");
+    if constexpr (is_golay(CODEC))
+      return &paged_attn_golay_mfma_kernel<G, CODEC == KVECC_CODEC_GOLAY_PACKED>;
+    else
+      return &paged_attn_h84_mfma_kernel<D, G>;
   }
-  if (!a.ctr) launch_combine<__half>(a, batch, st);
-  return KVECC_OK;
 }
 
-static int launch_mfma(int codec, const AttnArgs &a, int64_t batch, int gm, hipStream_t st) {
-  if (codec != KVECC_CODEC_H84) {  // Golay, head_dim 128 (attn_mfma_heads)
-    if (codec == KVECC_CODEC_GOLAY_PACKED) return launch_golay_mfma<true>(a, batch, gm, st);
-    return launch_golay_mfma<false>(a, batch, gm, st);
-  }
-  switch (a.d) {
-    case 32: return launch_mfma_d<32>(a, batch, gm, st);
-    case 64: return launch_mfma_d<64>(a, batch, gm, st);
-    default: return launch_mfma_d<128>(a, batch, gm, st);
-  }
-}
-// the byte family's decode kernels (Hamming(8,4)'s domain and geometry)
-static int launch_byte_mfma(const ByteAttnArgs &a, int64_t batch, int gm, hipStream_t st) {
-  switch (a.d) {
-    case 32: return launch_mfma_d<32>(a, batch, gm, st);
-    case 64: return launch_mfma_d<64>(a, batch, gm, st);
-    default: return launch_mfma_d<128>(a, batch, gm, st);
-  }
+template <typename A>
+static int launch_decode_mfma(const char *entry, int codec, const A &a, int64_t batch, int gm, hipStream_t st) {
+  const dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gm));
+  auto launch = [&](auto c, auto d, auto g) {
+    constexpr int CODEC = decltype(c)::value, G = decltype(g)::value;
+    if constexpr (is_golay(CODEC) && G == 1) {  // Golay MHA stays on the split kernels (attn_mfma_heads)
+      return set_error(KVECC_EINVAL, "%s: no Golay matrix-core kernel for one query head per workgroup", entry);
+    } else {
+      KVECC_LAUNCH((decode_mfma_kernel<A, CODEC, decltype(d)::value, G>()), grid, dim3(kBlock), 0, st, a);
+      return (int)KVECC_OK;
+    }
+  };
+  const int rc = with_codec<A>(entry, codec, [&](auto c) {
+    return with_head_dim(a.d, [&](auto d) {
+      switch (gm) {
+        case 1: return launch(c, d, int_tag<1>{});
+        case 2: return launch(c, d, int_tag<2>{});
+        case 4: return launch(c, d, int_tag<4>{});
+        case 8: return launch(c, d, int_tag<8>{});
+        default: return launch(c, d, int_tag<16>{});
+      }
+    });
+  });
+  if (rc != KVECC_OK) return rc;
+  if (!a.ctr) launch_combine<__half>(a, batch, st);
+  return KVECC_OK;
 }
 
 // query heads per workgroup of the MFMA kernels (0: not applicable): caches under
@@ -1303,33 +1382,6 @@ static int attn_mfma_heads(int codec, int q_dtype, const void *query, int64_t d,
   return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
 }
 
-template <typename T, typename A>
-static int launch_codec(int codec, const A &a, int64_t batch, int gq, hipStream_t st, bool combine = true) {
-  switch (codec) {
-    case KVECC_CODEC_H84: return launch_attn<T, KVECC_CODEC_H84>(a, batch, gq, st, combine);
-    case KVECC_CODEC_GOLAY: return launch_attn<T, KVECC_CODEC_GOLAY>(a, batch, gq, st, combine);
-    default: return launch_attn<T, KVECC_CODEC_GOLAY_PACKED>(a, batch, gq, st, combine);
-  }
-}
-
-// The general path of a chunked call: the split kernels over the virtual batch
-// of `rows` = batch * q_len query rows (AttnArgs::q_len), in slices that fit
-// grid.y, then one combine over all rows.
-constexpr int64_t kMaxGridY = 65535;
-template <typename T>
-static int launch_codec_rows(int codec, RaggedArgs a, int64_t rows, int gq, hipStream_t st) {
-  const int64_t wg_per_row = a.heads / gq;
-  if (rows * wg_per_row <= kMaxGridY) return launch_codec<T>(codec, a, rows, gq, st);
-  const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
-  for (int64_t vb = 0; vb < rows; vb += per) {
-    a.vb0 = (uint32_t)vb;
-    const int rc = launch_codec<T>(codec, a, std::min(per, rows - vb), gq, st, false);
-    if (rc != KVECC_OK) return rc;
-  }
-  launch_combine<T>(a, rows, st);
-  return KVECC_OK;
-}
-
 // heads per column group of the matrix-core chunk kernels (0: the general
 // path): attn_mfma_heads' domain with every query row 16-byte aligned, Golay
 // MHA included -- a decoded row serves 16 query columns here, so its decode
@@ -1345,141 +1397,67 @@ static int attn_chunk_mfma_heads(int codec, int q_dtype, const void *query, int6
   return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
 }
 
-static int launch_mfma_chunk(int codec, const RaggedArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
-  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
-  if (a.q_spans) {  // the ragged entry's kernels
-    if (codec == KVECC_CODEC_GOLAY_PACKED) {
-      KVECC_LAUNCH((paged_attn_golay_mfma_ragged_kernel<true>), grid, dim3(kBlock), 0, st, a);
-    } else if (codec == KVECC_CODEC_GOLAY) {
-      KVECC_LAUNCH((paged_attn_golay_mfma_ragged_kernel<false>), grid, dim3(kBlock), 0, st, a);
+// The matrix-core tile kernel of a chunked call's (block, codec, head_dim); Golay:
+// head_dim 128 (attn_chunk_mfma_heads).  The uniform kernels take the narrower
+// blocks ChunkArgs / ByteUniformArgs (see RaggedArgs, ByteUniformArgs).
+template <typename A, int CODEC, int D>
+constexpr auto tile_kernel() {
+  if constexpr (is_golay(CODEC)) {
+    constexpr bool PACKED = CODEC == KVECC_CODEC_GOLAY_PACKED;
+    if constexpr (std::is_same<A, ChunkArgs>::value) {
+      return &paged_attn_golay_mfma_chunk_kernel<PACKED>;
+    } else if constexpr (std::is_same<A, RaggedArgs>::value) {
+      return &paged_attn_golay_mfma_ragged_kernel<PACKED>;
     } else {
-      switch (a.d) {
-        case 32: KVECC_LAUNCH((paged_attn_h84_mfma_ragged_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
-        case 64: KVECC_LAUNCH((paged_attn_h84_mfma_ragged_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
-        default: KVECC_LAUNCH((paged_attn_h84_mfma_ragged_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
-      }
+      static_assert(std::is_same<A, StatsArgs>::value, "no Golay tile kernel takes this block");
+      return &paged_attn_golay_mfma_stats_kernel<PACKED>;
     }
-    launch_combine<__half>(a, batch * a.q_len, st);
-    return KVECC_OK;
-  }
-  const ChunkArgs &u = a;  // the uniform kernels' argument block
-  if (codec == KVECC_CODEC_GOLAY_PACKED) {
-    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<true>), grid, dim3(kBlock), 0, st, u);
-  } else if (codec == KVECC_CODEC_GOLAY) {
-    KVECC_LAUNCH((paged_attn_golay_mfma_chunk_kernel<false>), grid, dim3(kBlock), 0, st, u);
+  } else if constexpr (std::is_same<A, ChunkArgs>::value) {
+    return &paged_attn_h84_mfma_chunk_kernel<D>;
+  } else if constexpr (std::is_same<A, RaggedArgs>::value) {
+    return &paged_attn_h84_mfma_ragged_kernel<D>;
+  } else if constexpr (std::is_same<A, InterpArgs>::value) {
+    return &paged_attn_h84_mfma_interp_kernel<D>;
+  } else if constexpr (std::is_same<A, StatsArgs>::value) {
+    return &paged_attn_h84_mfma_stats_kernel<D>;
+  } else if constexpr (std::is_same<A, StatsInterpArgs>::value) {
+    return &paged_attn_h84_mfma_stats_interp_kernel<D>;
+  } else if constexpr (std::is_same<A, RepairArgs>::value) {
+    return &paged_attn_h84_mfma_repair_kernel<D>;
+  } else if constexpr (std::is_same<A, RepairInterpArgs>::value) {
+    return &paged_attn_h84_mfma_repair_interp_kernel<D>;
+  } else if constexpr (std::is_same<A, ByteUniformArgs>::value) {
+    return &paged_attn_byte_mfma_chunk_kernel<D>;
   } else {
-    switch (a.d) {
-      case 32: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<32>), grid, dim3(kBlock), 0, st, u); break;
-      case 64: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<64>), grid, dim3(kBlock), 0, st, u); break;
-      default: KVECC_LAUNCH((paged_attn_h84_mfma_chunk_kernel<128>), grid, dim3(kBlock), 0, st, u); break;
-    }
+    static_assert(std::is_same<A, ByteChunkArgs>::value, "no tile kernel takes this block");
+    return &paged_attn_byte_mfma_ragged_kernel<D>;
   }
-  launch_combine<__half>(a, batch * a.q_len, st);
-  return KVECC_OK;
 }
 
-// the byte family's matrix-core chunk kernels: the ragged entry's or the uniform ones
-static int launch_byte_mfma_chunk(const ByteChunkArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
-  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
-  if (a.q_spans) {
-    switch (a.d) {
-      case 32: KVECC_LAUNCH((paged_attn_byte_mfma_ragged_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
-      case 64: KVECC_LAUNCH((paged_attn_byte_mfma_ragged_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
-      default: KVECC_LAUNCH((paged_attn_byte_mfma_ragged_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
-    }
-  } else {
-    ByteUniformArgs u;  // the uniform kernels' argument block
-    static_cast<ChunkArgs &>(u) = a;
-    u.tab = a.tab;
-    switch (a.d) {
-      case 32: KVECC_LAUNCH((paged_attn_byte_mfma_chunk_kernel<32>), grid, dim3(kBlock), 0, st, u); break;
-      case 64: KVECC_LAUNCH((paged_attn_byte_mfma_chunk_kernel<64>), grid, dim3(kBlock), 0, st, u); break;
-      default: KVECC_LAUNCH((paged_attn_byte_mfma_chunk_kernel<128>), grid, dim3(kBlock), 0, st, u); break;
-    }
-  }
-  launch_combine<__half>(a, batch * a.q_len, st);
-  return KVECC_OK;
-}
-
-// the interpolating entry's matrix-core kernels (uniform calls too: the spans are nullable)
-static int launch_mfma_interp(const InterpArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
-  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
-  switch (a.d) {
-    case 32: KVECC_LAUNCH((paged_attn_h84_mfma_interp_kernel<32>), grid, dim3(kBlock), 0, st, a); break;
-    case 64: KVECC_LAUNCH((paged_attn_h84_mfma_interp_kernel<64>), grid, dim3(kBlock), 0, st, a); break;
-    default: KVECC_LAUNCH((paged_attn_h84_mfma_interp_kernel<128>), grid, dim3(kBlock), 0, st, a); break;
-  }
-  launch_combine<__half>(a, batch * a.q_len, st);
-  return KVECC_OK;
-}
-// the counted entry's matrix-core kernels (uniform calls too: the spans are nullable), and the
-// repairing entry's (A RepairArgs / RepairInterpArgs): the same grid
+// The matrix-core path of a chunked call: block A's tile kernel over `tiles`
+// 16-column tiles per (sequence, head group), then the combine.  A uniform call of
+// the plain and the byte kernels (no spans) hands over the narrower block.
 template <typename A>
-static int launch_mfma_stats(const A &a, int64_t batch, int64_t tiles, hipStream_t st) {
+static int launch_tiles(const char *entry, int codec, const A &a, int64_t batch, int64_t tiles, hipStream_t st) {
+  if constexpr (std::is_same<A, RaggedArgs>::value) {
+    if (!a.q_spans) return launch_tiles<ChunkArgs>(entry, codec, a, batch, tiles, st);
+  } else if constexpr (std::is_same<A, ByteChunkArgs>::value) {
+    if (!a.q_spans) {
+      ByteUniformArgs u;
+      static_cast<ChunkArgs &>(u) = a;
+      u.tab = a.tab;
+      return launch_tiles(entry, codec, u, batch, tiles, st);
+    }
+  }
   const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
-#define KVECC_MFMA_STATS_LAUNCH(D_)                                                                  \
-  do {                                                                                               \
-    if constexpr (std::is_same<A, RepairInterpArgs>::value)                                          \
-      KVECC_LAUNCH((paged_attn_h84_mfma_repair_interp_kernel<D_>), grid, dim3(kBlock), 0, st, a);    \
-    else if constexpr (std::is_same<A, RepairArgs>::value)                                           \
-      KVECC_LAUNCH((paged_attn_h84_mfma_repair_kernel<D_>), grid, dim3(kBlock), 0, st, a);           \
-    else if constexpr (std::is_same<A, StatsInterpArgs>::value)                                      \
-      KVECC_LAUNCH((paged_attn_h84_mfma_stats_interp_kernel<D_>), grid, dim3(kBlock), 0, st, a);     \
-    else                                                                                             \
-      KVECC_LAUNCH((paged_attn_h84_mfma_stats_kernel<D_>), grid, dim3(kBlock), 0, st, a);            \
-  } while (0)
-  switch (a.d) {
-    case 32: KVECC_MFMA_STATS_LAUNCH(32); break;
-    case 64: KVECC_MFMA_STATS_LAUNCH(64); break;
-    default: KVECC_MFMA_STATS_LAUNCH(128); break;
-  }
-#undef KVECC_MFMA_STATS_LAUNCH
+  const int rc = with_codec<A>(entry, codec, [&](auto c) {
+    return with_head_dim(a.d, [&](auto d) {
+      KVECC_LAUNCH((tile_kernel<A, decltype(c)::value, decltype(d)::value>()), grid, dim3(kBlock), 0, st, a);
+      return (int)KVECC_OK;
+    });
+  });
+  if (rc != KVECC_OK) return rc;
   launch_combine<__half>(a, batch * a.q_len, st);
-  return KVECC_OK;
-}
-// the Golay counted entry's matrix-core kernels and its general path (launch_codec_rows over a
-// StatsArgs: the virtual batch in slices that fit grid.y, then one combine)
-static int launch_golay_mfma_stats(int codec, const StatsArgs &a, int64_t batch, int64_t tiles, hipStream_t st) {
-  const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
-  if (codec == KVECC_CODEC_GOLAY_PACKED)
-    KVECC_LAUNCH((paged_attn_golay_mfma_stats_kernel<true>), grid, dim3(kBlock), 0, st, a);
-  else
-    KVECC_LAUNCH((paged_attn_golay_mfma_stats_kernel<false>), grid, dim3(kBlock), 0, st, a);
-  launch_combine<__half>(a, batch * a.q_len, st);
-  return KVECC_OK;
-}
-template <typename T>
-static int launch_golay_stats_rows(int codec, StatsArgs a, int64_t rows, int gq, hipStream_t st) {
-  const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
-  auto launch = [&](int64_t n, bool combine) {
-    return packed ? launch_attn<T, KVECC_CODEC_GOLAY_PACKED>(a, n, gq, st, combine)
-                  : launch_attn<T, KVECC_CODEC_GOLAY>(a, n, gq, st, combine);
-  };
-  const int64_t wg_per_row = a.heads / gq;
-  if (rows * wg_per_row <= kMaxGridY) return launch(rows, true);
-  const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
-  for (int64_t vb = 0; vb < rows; vb += per) {
-    a.vb0 = (uint32_t)vb;
-    const int rc = launch(std::min(per, rows - vb), false);
-    if (rc != KVECC_OK) return rc;
-  }
-  launch_combine<T>(a, rows, st);
-  return KVECC_OK;
-}
-// The Hamming(8,4) layout's general path: launch_codec_rows for the interpolating split kernels
-// (A InterpArgs), for the byte family's (A ByteChunkArgs), for the counted
-// ones (A StatsArgs / StatsInterpArgs) and for the repairing ones (A RepairArgs / RepairInterpArgs)
-template <typename T, typename A>
-static int launch_h84_rows(A a, int64_t rows, int gq, hipStream_t st) {
-  const int64_t wg_per_row = a.heads / gq;
-  if (rows * wg_per_row <= kMaxGridY) return launch_attn<T, KVECC_CODEC_H84>(a, rows, gq, st);
-  const int64_t per = kMaxGridY / wg_per_row;  // >= 1: checked by the caller
-  for (int64_t vb = 0; vb < rows; vb += per) {
-    a.vb0 = (uint32_t)vb;
-    const int rc = launch_attn<T, KVECC_CODEC_H84>(a, std::min(per, rows - vb), gq, st, false);
-    if (rc != KVECC_OK) return rc;
-  }
-  launch_combine<T>(a, rows, st);
   return KVECC_OK;
 }
 
@@ -1495,6 +1473,314 @@ static int64_t choose_split(int64_t bh, int64_t max_context_len, int per_cu = 4)
   while (split > 32 && bh * cdiv(max_context_len, split) < want) split >>= 1;
   while (cdiv(max_context_len, split) > kMaxSplits && split < top) split <<= 1;
   return split;
+}
+
+// The finest split a chunked call can pick: its matrix-core grid has at least
+// rows / 16 workgroups per split (16 query rows per tile), the split kernels'
+// rows / 4.
+static int64_t chunk_finest_split(int64_t rows, int64_t max_context_len) {
+  return choose_split(std::max<int64_t>(1, rows / 16), max_context_len);
+}
+
+// ---- the entries' shared front half ----------------------------------------------
+// A call's parameters, in the order and under the names of kvecc.h's chunk-family
+// entries (the decode entry: q_len 1, no spans, its strides unused).
+struct AttnCall {
+  const void *query;
+  int64_t q_sb, q_st, q_sh;
+  int q_dtype;
+  const void *k_cache, *v_cache;
+  const int32_t *block_table, *context_lens, *q_spans;
+  const float *k_scales, *v_scales;
+  void *out;
+  int64_t batch, q_len, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks;
+  int64_t max_context_len;
+  float sm_scale;
+  int codec;
+  float *workspace;
+  int64_t workspace_floats;
+  void *stream;
+};
+
+// What an entry decides between the argument fill and the split count (attn_setup's
+// `plan`, which also sets a.split and, in a chunked call, a.cg_log2)
+struct AttnPlan {
+  int gq = 1, gm = 0;  // query heads per workgroup: the split kernels', the matrix-core kernels' (0: not taken)
+  int64_t tiles = 1;   // matrix-core chunk kernels: 16-column tiles per (sequence, head group)
+  bool ctr = false;    // the fused combine (AttnArgs::ctr)
+};
+
+// Validation and argument fill of every attention entry, in the order the messages
+// have always come in.  A: ByteAttnArgs (the decode entry) or ByteChunkArgs -- the
+// byte family's blocks, which hold every other codec's (AttnArgs / RaggedArgs) as
+// their base.  codec: the call's; on return the kernels' (the byte family runs as
+// Hamming(8,4): kvecc.h).  plan(a, fits, max_context_len, p) is the entry's choice
+// of kernels and split size, `fits` saying that the caches are buffer-addressable.
+template <typename A, typename Plan>
+static int attn_setup(const char *entry, const AttnCall &c, int &codec, A &a, AttnPlan &p, Plan &&plan) {
+  if (c.kv_heads < 1 || c.heads % c.kv_heads != 0)
+    return set_error(KVECC_EINVAL, "%s: %lld heads not a multiple of %lld kv heads", entry, (long long)c.heads,
+                     (long long)c.kv_heads);
+  if (c.head_dim < 1 || c.head_dim > kAttnMaxD)
+    return set_error(KVECC_EINVAL, "%s: head_dim %lld not in [1, %d]", entry, (long long)c.head_dim, kAttnMaxD);
+  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
+      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL, "%s: codec %d (int4, hamming74, hamming84, golay or golay_packed only)", entry,
+                     codec);
+  // the byte family (kvecc.h): Hamming(8,4)'s layout, rules and launch geometry, its own kernels
+  const int table = codec;
+  if (codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74) codec = KVECC_CODEC_H84;
+  if (codec == KVECC_CODEC_H84 && c.head_dim % 4 != 0)
+    return set_error(KVECC_EINVAL, "%s: %s head_dim must be a multiple of 4", entry,
+                     table == KVECC_CODEC_NONE ? "int4" : table == KVECC_CODEC_H74 ? "hamming74" : "hamming84");
+  if constexpr (is_chunk<A>)  // (the decode entry names a bad dtype last, where it dispatches on it)
+    if (c.q_dtype != KVECC_F32 && c.q_dtype != KVECC_F16 && c.q_dtype != KVECC_BF16)
+      return set_error(KVECC_EINVAL, "%s: bad dtype %d", entry, c.q_dtype);
+  if (c.num_layers < 1 || c.layer < 0 || c.layer >= c.num_layers || c.block_size < 1 || c.max_blocks < 1)
+    return set_error(KVECC_EINVAL, "%s: bad cache geometry", entry);
+  const int64_t rows_total = c.num_blocks * c.num_layers * c.kv_heads * c.block_size;
+  if (c.num_blocks < 1 || rows_total > 0x7FFFFFFFLL)
+    return set_error(KVECC_EINVAL, "%s: cache rows must fit int32", entry);
+  const int64_t max_context_len = c.max_context_len <= 0 ? c.max_blocks * c.block_size : c.max_context_len;
+  if (!c.query || !c.k_cache || !c.v_cache || !c.block_table || !c.context_lens || !c.k_scales || !c.v_scales ||
+      !c.out || !c.workspace)
+    return set_error(KVECC_EINVAL, "%s: null pointer", entry);
+  if constexpr (is_chunk<A>) {
+    const int64_t vbatch = c.batch * c.q_len;  // query rows per head: the virtual batch
+    if (c.q_len > 0x7FFFFFFFLL || vbatch > 0x7FFFFFFFLL || vbatch * c.heads > 0x7FFFFFFFLL)
+      return set_error(KVECC_EINVAL, "%s: %lld x %lld x %lld query rows exceed the grid", entry, (long long)c.batch,
+                       (long long)c.q_len, (long long)c.heads);
+  }
+  // (q_len 1: kvecc_paged_attention_workspace, the decode entry's bound)
+  const int64_t need =
+      kvecc_paged_attention_chunk_workspace(c.batch, c.q_len, c.heads, c.head_dim, max_context_len);
+  if (c.workspace_floats < need)
+    return set_error(KVECC_EINVAL, "%s: workspace %lld < %lld floats", entry, (long long)c.workspace_floats,
+                     (long long)need);
+  a.tab = (uint32_t)table;
+  a.q = c.query;
+  a.k_cache = c.k_cache;
+  a.v_cache = c.v_cache;
+  a.table = c.block_table;
+  a.ctx_lens = c.context_lens;
+  a.k_scales = c.k_scales;
+  a.v_scales = c.v_scales;
+  a.ws = c.workspace;
+  a.out = c.out;
+  a.heads = c.heads;
+  a.kv_heads = c.kv_heads;
+  a.d = c.head_dim;
+  a.g = codec == KVECC_CODEC_H84 ? c.head_dim / 4 : (c.head_dim + 2) / 3;
+  a.rowb = (uint32_t)KVECC_GOLAY_PACKED_ROW(a.g);
+  a.layers = c.num_layers;
+  a.layer = c.layer;
+  a.bs = c.block_size;
+  a.max_blocks = c.max_blocks;
+  a.ctx_cap = std::min(max_context_len, c.max_blocks * c.block_size);
+  a.sm_scale = c.sm_scale;
+  a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
+  if constexpr (is_chunk<A>) {
+    a.q_len = (uint32_t)c.q_len;
+    a.vb0 = 0;
+    a.q_sb = c.q_sb;
+    a.q_st = c.q_st;
+    a.q_sh = c.q_sh;
+    a.cg_log2 = 0;
+    a.q_spans = c.q_spans;
+  }
+  const int64_t cb = rows_total * (codec == KVECC_CODEC_H84            ? c.head_dim
+                                   : codec == KVECC_CODEC_GOLAY_PACKED ? (int64_t)a.rowb
+                                                                       : 4 * a.g);
+  const bool fits = cb <= 0xFFFFFFFFLL && rows_total * 4 <= 0xFFFFFFFFLL;
+  a.cache_bytes = fits ? (uint32_t)cb : 0u;  // 0 selects the 64-bit-addressed kernels
+  a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
+  const int rc = plan(a, fits, max_context_len, p);
+  if (rc != KVECC_OK) return rc;
+  a.nsplit = cdiv(max_context_len, a.split);
+  if (a.nsplit > kMaxSplits)
+    return set_error(KVECC_EINVAL, "%s: context %lld too long", entry, (long long)max_context_len);
+  if (p.gm && a.nsplit * p.tiles > 0x7FFFFFFFLL)
+    return set_error(KVECC_EINVAL, "%s: %lld splits x %lld tiles exceed the grid", entry, (long long)a.nsplit,
+                     (long long)p.tiles);
+  a.par = a.cor = nullptr;
+  a.atab = a.atab_x = nullptr;
+  a.ctr = nullptr;
+  if (p.ctr) {
+    a.ctr = attn_counter_slot(c.stream);
+    if (!a.ctr) return KVECC_EHIP;
+  }
+  if (codec != KVECC_CODEC_H84) {
+    a.par = golay_parity_table_dev();
+    a.cor = golay_correct_table_dev();
+    a.atab = golay_attn_table_dev();
+    a.atab_x = golay_attn_x_table_dev();
+    if (!a.par || !a.cor || !a.atab || !a.atab_x) return KVECC_EHIP;
+  }
+  return KVECC_OK;
+}
+
+// ---- the decode entry --------------------------------------------------------------
+static int paged_attention_decode(const AttnCall &c) {
+  const char *entry = "paged_attention";
+  if (c.batch < 0 || c.heads < 0 || c.kv_heads < 0 || c.head_dim < 0)
+    return set_error(KVECC_EINVAL, "paged_attention: negative size");
+  if (c.batch == 0 || c.heads == 0) return KVECC_OK;
+  int codec = c.codec;
+  ByteAttnArgs a;  // AttnArgs for every other codec's kernels
+  AttnPlan p;
+  const int rc = attn_setup(entry, c, codec, a, p, [&](ByteAttnArgs &a, bool fits, int64_t max_context_len, AttnPlan &p) {
+    p.gq = attn_heads_per_wg(codec, c.head_dim, a.g, c.heads, c.kv_heads, fits);
+    p.gm = attn_mfma_heads(codec, c.q_dtype, c.query, c.head_dim, c.heads, c.kv_heads, fits);
+    if (p.gm)  // kMfma*WgPerCu workgroups per CU, never finer than the workspace allows
+      a.split = std::max(choose_split(c.batch * c.heads / p.gm, max_context_len,
+                                      codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu : kMfmaWgPerCu),
+                         choose_split(std::max<int64_t>(1, c.batch * c.heads / 4), max_context_len));
+    else
+      a.split = choose_split(c.batch * c.heads / p.gq, max_context_len);
+    // fused combine for one query head per workgroup only (MHA 59.7 -> 58.9 us).
+    // With G heads the tail after the last split -- the sc1 stores' acknowledgement,
+    // the counter's round trip and rounds of sc1 loads, which bypass the L2 -- cost
+    // more than the combine launch: 32q/8kv 22.6 -> 32.8 us with the G heads
+    // combined serially, 26.9 with one wave per head, 26.7 (against 22.3) with all
+    // G heads in one round trip (combine_group; profiles/r03/attn/).
+    const int gw = p.gm ? p.gm : p.gq;  // query heads per workgroup
+    p.ctr = gw == 1 && c.batch * c.heads <= kAttnCtrPerSlot;
+    return (int)KVECC_OK;
+  });
+  if (rc != KVECC_OK) return rc;
+  hipStream_t st = as_stream(c.stream);
+  auto run = [&](const auto &b) {  // b: the block of the codec's kernels
+    using B = std::decay_t<decltype(b)>;
+    if (p.gm) return launch_decode_mfma(entry, codec, b, c.batch, p.gm, st);
+    return with_q_dtype(entry, c.q_dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return with_codec<B>(entry, codec,
+                           [&](auto cd) { return launch_attn<T, decltype(cd)::value>(entry, b, c.batch, p.gq, st); });
+    });
+  };
+  const bool bytes = c.codec == KVECC_CODEC_NONE || c.codec == KVECC_CODEC_H74;
+  const int lrc = bytes ? run(a) : run(static_cast<const AttnArgs &>(a));
+  if (lrc != KVECC_OK) return lrc;
+  return check_launch("paged_attention");
+}
+
+// ---- chunked causal attention ---------------------------------------------------
+// Which chunk-family entry a call came through.  q_spans (AttnCall) is null for
+// kvecc_paged_attention_chunk and the device spans for the ragged entry (q_len its
+// q_max); nothing but the kernels reads the spans: the launch geometry is the
+// uniform call's.
+enum class AttnKind {
+  plain,          // kvecc_paged_attention_chunk / _chunk_ragged / _interp
+  counted,        // kvecc_paged_attention_stats: Hamming(8,4), stats[0..1]
+  golay_counted,  // kvecc_paged_attention_golay_stats: golay / golay_packed, no interpolation
+  repair,         // kvecc_paged_attention_repair: the counted call's geometry and argument values
+                  // over the repairing kernels, stats[2] too
+};
+struct AttnMode {
+  AttnKind kind = AttnKind::plain;
+  // Hamming(8,4) caches under 4 GiB through the interpolating kernels at every q_len (q_len 1
+  // included: the decode entry's kernels do not interpolate)
+  bool interp = false;
+  uint64_t *stats = nullptr;  // the library's sharded statistics buffer: every kind but plain
+};
+static const char *mode_entry(const AttnMode &m) {
+  switch (m.kind) {
+    case AttnKind::golay_counted: return "paged_attention_golay_stats";
+    case AttnKind::repair: return "paged_attention_repair";
+    case AttnKind::counted: return "paged_attention_stats";
+    default: return m.interp ? "paged_attention_interp" : "paged_attention_chunk";
+  }
+}
+
+static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
+  const char *entry = "paged_attention_chunk";
+  if (c.batch < 0 || c.q_len < 0 || c.heads < 0 || c.kv_heads < 0 || c.head_dim < 0)
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
+  // the mode's legal combinations (the entries have checked their own codec and buffer first)
+  const bool counts = m.kind != AttnKind::plain;
+  if (counts != (m.stats != nullptr) || (m.kind == AttnKind::golay_counted && m.interp))
+    return set_error(KVECC_EINVAL, "%s: illegal mode (kind %d, interp %d, stats %s)", mode_entry(m), (int)m.kind,
+                     (int)m.interp, m.stats ? "set" : "null");
+  int codec = c.codec;
+  if (counts && m.kind != AttnKind::golay_counted && codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
+  if (m.interp && codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
+  if (c.batch == 0 || c.q_len == 0 || c.heads == 0) return KVECC_OK;
+  if (c.q_sb < 0 || c.q_st < 0 || c.q_sh < 0 || (c.heads > 1 && c.q_sh < c.head_dim) ||
+      (c.q_len > 1 && c.q_st < c.head_dim))
+    return set_error(KVECC_EINVAL, "paged_attention_chunk: query strides (%lld, %lld, %lld) for head_dim %lld",
+                     (long long)c.q_sb, (long long)c.q_st, (long long)c.q_sh, (long long)c.head_dim);
+  // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
+  // (a ragged call stays here: the decode entry knows no spans)
+  if (!m.interp && !counts && !c.q_spans && c.q_len == 1 && (c.heads == 1 || c.q_sh == c.head_dim) &&
+      (c.batch == 1 || c.q_sb == c.heads * c.head_dim))
+    return paged_attention_decode(c);
+  const int64_t vbatch = c.batch * c.q_len;  // query rows per head: the virtual batch
+  ByteChunkArgs a;  // RaggedArgs for every other codec's kernels; a mode's own block is a copy, below
+  AttnPlan p;
+  const int rc = attn_setup(entry, c, codec, a, p, [&](ByteChunkArgs &a, bool fits, int64_t max_context_len, AttnPlan &p) {
+    if (m.interp && !fits)
+      return set_error(KVECC_EINVAL, "paged_attention_interp: caches of 4 GiB or more are not supported");
+    if (counts && !fits)
+      return set_error(KVECC_EINVAL, "%s: caches of 4 GiB or more are not supported", mode_entry(m));
+    p.gq = attn_heads_per_wg(codec, c.head_dim, a.g, c.heads, c.kv_heads, fits);
+    // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound);
+    // an interpolating call takes its matrix-core kernels at q_len 1 too (one tile, the same bound: `finest`)
+    // (a counted call takes its matrix-core kernels at every q_len too)
+    p.gm = c.q_len > 1 || m.interp || counts
+               ? attn_chunk_mfma_heads(codec, c.q_dtype, c.query, c.q_sb, c.q_st, c.q_sh, c.head_dim, c.heads,
+                                       c.kv_heads, fits)
+               : 0;
+    // (a counted Golay decode step without GQA stays on the split kernels, as the decode entry's does: attn_mfma_heads)
+    if (m.kind == AttnKind::golay_counted && c.q_len == 1 && c.heads == c.kv_heads) p.gm = 0;
+    int64_t wgs = 0;  // workgroups per split
+    if (p.gm) {
+      for (a.cg_log2 = 0; (1 << a.cg_log2) < p.gm; ++a.cg_log2) {}
+      p.tiles = cdiv(c.q_len, 16 / p.gm);
+      wgs = c.batch * (c.heads / p.gm) * p.tiles;
+      if (c.batch * (c.heads / p.gm) > kMaxGridY) p.gm = 0;  // the split kernels slice their grid
+    }
+    if (!p.gm) {
+      a.cg_log2 = 0;
+      wgs = vbatch * c.heads / p.gq;
+      if (c.heads / p.gq > kMaxGridY)
+        return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld heads exceed the grid", (long long)c.heads);
+    }
+    const int64_t finest = c.q_len > 1
+                               ? chunk_finest_split(vbatch * c.heads, max_context_len)
+                               : choose_split(std::max<int64_t>(1, c.batch * c.heads / 4), max_context_len);
+    a.split = std::max(choose_split(wgs, max_context_len,
+                                    !p.gm                      ? 4
+                                    : codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu
+                                                               : kMfmaWgPerCu),
+                       finest);
+    // the counted combine as in the decode entry: one query head per workgroup of the split kernels
+    p.ctr = !p.gm && p.gq == 1 && vbatch * c.heads <= kAttnCtrPerSlot;
+    return (int)KVECC_OK;
+  });
+  if (rc != KVECC_OK) return rc;
+  hipStream_t st = as_stream(c.stream);
+  // the block the mode's kernels take, then its matrix-core tiles or the general path
+  auto run = [&](auto b) {
+    using B = decltype(b);
+    if constexpr (!is_byte<B>) static_cast<RaggedArgs &>(b) = a;
+    if constexpr (is_stats<B> || is_repair<B>) b.stats = m.stats;
+    if (p.gm) return launch_tiles(mode_entry(m), codec, b, c.batch, p.tiles, st);
+    return with_q_dtype(mode_entry(m), c.q_dtype, [&](auto t) {
+      return launch_rows<typename decltype(t)::type>(mode_entry(m), codec, b, vbatch, p.gq, st);
+    });
+  };
+  const bool bytes = c.codec == KVECC_CODEC_NONE || c.codec == KVECC_CODEC_H74;
+  int lrc;
+  switch (m.kind) {
+    case AttnKind::golay_counted: lrc = run(StatsArgs{}); break;
+    case AttnKind::repair: lrc = m.interp ? run(RepairInterpArgs{}) : run(RepairArgs{}); break;
+    case AttnKind::counted: lrc = m.interp ? run(StatsInterpArgs{}) : run(StatsArgs{}); break;
+    default: lrc = m.interp ? run(InterpArgs{}) : bytes ? run(a) : run(RaggedArgs{}); break;
+  }
+  if (lrc != KVECC_OK) return lrc;
+  return check_launch("paged_attention_chunk");
 }
 
 }  // namespace kvecc
@@ -1521,136 +1807,10 @@ KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *
                                     int64_t max_blocks, int64_t max_context_len, float sm_scale,
                                     int codec, float *workspace, int64_t workspace_floats,
                                     void *stream) {
-  if (batch < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
-    return set_error(KVECC_EINVAL, "paged_attention: negative size");
-  if (batch == 0 || heads == 0) return KVECC_OK;
-  if (kv_heads < 1 || heads % kv_heads != 0)
-    return set_error(KVECC_EINVAL, "paged_attention: %lld heads not a multiple of %lld kv heads",
-                     (long long)heads, (long long)kv_heads);
-  if (head_dim < 1 || head_dim > kAttnMaxD)
-    return set_error(KVECC_EINVAL, "paged_attention: head_dim %lld not in [1, %d]", (long long)head_dim, kAttnMaxD);
-  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
-      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL, "paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed only)",
-                     codec);
-  // the byte family (kvecc.h): Hamming(8,4)'s layout, rules and launch geometry, its own kernels
-  const bool bytes = codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74;
-  const int table = codec;
-  if (bytes) codec = KVECC_CODEC_H84;
-  if (codec == KVECC_CODEC_H84 && head_dim % 4 != 0)
-    return set_error(KVECC_EINVAL, "paged_attention: %s head_dim must be a multiple of 4",
-                     table == KVECC_CODEC_NONE ? "int4" : table == KVECC_CODEC_H74 ? "hamming74" : "hamming84");
-  if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
-    return set_error(KVECC_EINVAL, "paged_attention: bad cache geometry");
-  if (num_blocks < 1 || num_blocks * num_layers * kv_heads * block_size > 0x7FFFFFFFLL)
-    return set_error(KVECC_EINVAL, "paged_attention: cache rows must fit int32");
-  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
-  if (!query || !k_cache || !v_cache || !block_table || !context_lens || !k_scales || !v_scales ||
-      !out || !workspace)
-    return set_error(KVECC_EINVAL, "paged_attention: null pointer");
-  const int64_t need = kvecc_paged_attention_workspace(batch, heads, head_dim, max_context_len);
-  if (workspace_floats < need)
-    return set_error(KVECC_EINVAL, "paged_attention: workspace %lld < %lld floats",
-                     (long long)workspace_floats, (long long)need);
-  ByteAttnArgs a;  // AttnArgs for every other codec's kernels
-  a.tab = (uint32_t)table;
-  a.q = query;
-  a.k_cache = k_cache;
-  a.v_cache = v_cache;
-  a.table = block_table;
-  a.ctx_lens = context_lens;
-  a.k_scales = k_scales;
-  a.v_scales = v_scales;
-  a.ws = workspace;
-  a.out = out;
-  a.heads = heads;
-  a.kv_heads = kv_heads;
-  a.d = head_dim;
-  a.g = codec == KVECC_CODEC_H84 ? head_dim / 4 : (head_dim + 2) / 3;
-  a.rowb = (uint32_t)KVECC_GOLAY_PACKED_ROW(a.g);
-  a.layers = num_layers;
-  a.layer = layer;
-  a.bs = block_size;
-  a.max_blocks = max_blocks;
-  a.ctx_cap = std::min(max_context_len, max_blocks * block_size);
-  a.sm_scale = sm_scale;
-  a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
-  int gq = 1, gm = 0;
-  {
-    const int64_t rows_total = num_blocks * num_layers * kv_heads * block_size;
-    const int64_t cb = rows_total * (codec == KVECC_CODEC_H84            ? head_dim
-                                     : codec == KVECC_CODEC_GOLAY_PACKED ? (int64_t)a.rowb
-                                                                         : 4 * a.g);
-    const bool fits = cb <= 0xFFFFFFFFLL && rows_total * 4 <= 0xFFFFFFFFLL;
-    a.cache_bytes = fits ? (uint32_t)cb : 0u;  // 0 selects the 64-bit-addressed kernels
-    a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
-    gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
-    gm = attn_mfma_heads(codec, q_dtype, query, head_dim, heads, kv_heads, fits);
-  }
-  if (gm)  // kMfma*WgPerCu workgroups per CU, never finer than the workspace allows
-    a.split = std::max(choose_split(batch * heads / gm, max_context_len,
-                                    codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu : kMfmaWgPerCu),
-                       choose_split(std::max<int64_t>(1, batch * heads / 4), max_context_len));
-  else
-    a.split = choose_split(batch * heads / gq, max_context_len);
-  a.nsplit = cdiv(max_context_len, a.split);
-  if (a.nsplit > kMaxSplits)
-    return set_error(KVECC_EINVAL, "paged_attention: context %lld too long", (long long)max_context_len);
-  a.par = a.cor = nullptr;
-  a.atab = a.atab_x = nullptr;
-  a.ctr = nullptr;
-  // fused combine for one query head per workgroup only (MHA 59.7 -> 58.9 us).
-  // With G heads the tail after the last split -- the sc1 stores' acknowledgement,
-  // the counter's round trip and rounds of sc1 loads, which bypass the L2 -- cost
-  // more than the combine launch: 32q/8kv 22.6 -> 32.8 us with the G heads
-  // combined serially, 26.9 with one wave per head, 26.7 (against 22.3) with all
-  // G heads in one round trip (combine_group; profiles/r03/attn/).
-  const int gw = gm ? gm : gq;  // query heads per workgroup
-  if (gw == 1 && batch * heads <= kAttnCtrPerSlot) {
-    a.ctr = attn_counter_slot(stream);
-    if (!a.ctr) return KVECC_EHIP;
-  }
-  if (codec != KVECC_CODEC_H84) {
-    a.par = golay_parity_table_dev();
-    a.cor = golay_correct_table_dev();
-    a.atab = golay_attn_table_dev();
-    a.atab_x = golay_attn_x_table_dev();
-    if (!a.par || !a.cor || !a.atab || !a.atab_x) return KVECC_EHIP;
-  }
-  hipStream_t st = as_stream(stream);
-  if (gm) {
-    const int rc = bytes ? launch_byte_mfma(a, batch, gm, st) : launch_mfma(codec, a, batch, gm, st);
-    if (rc != KVECC_OK) return rc;
-    return check_launch("paged_attention");
-  }
-  int rc;
-  if (bytes) {
-    switch (q_dtype) {
-      case KVECC_F32: rc = launch_attn<float, KVECC_CODEC_H84>(a, batch, gq, st); break;
-      case KVECC_F16: rc = launch_attn<__half, KVECC_CODEC_H84>(a, batch, gq, st); break;
-      case KVECC_BF16: rc = launch_attn<__hip_bfloat16, KVECC_CODEC_H84>(a, batch, gq, st); break;
-      default: return set_error(KVECC_EINVAL, "paged_attention: bad dtype %d", q_dtype);
-    }
-    if (rc != KVECC_OK) return rc;
-    return check_launch("paged_attention");
-  }
-  const AttnArgs &o = a;  // every other codec's argument block
-  switch (q_dtype) {
-    case KVECC_F32: rc = launch_codec<float>(codec, o, batch, gq, st); break;
-    case KVECC_F16: rc = launch_codec<__half>(codec, o, batch, gq, st); break;
-    case KVECC_BF16: rc = launch_codec<__hip_bfloat16>(codec, o, batch, gq, st); break;
-    default: return set_error(KVECC_EINVAL, "paged_attention: bad dtype %d", q_dtype);
-  }
-  if (rc != KVECC_OK) return rc;
-  return check_launch("paged_attention");
-}
-
-// ---- chunked causal attention ---------------------------------------------------
-// The finest split a chunked call can pick: its matrix-core grid has at least
-// rows / 16 workgroups per split (16 query rows per tile), the split kernels'
-// rows / 4.
-static int64_t chunk_finest_split(int64_t rows, int64_t max_context_len) {
-  return choose_split(std::max<int64_t>(1, rows / 16), max_context_len);
+  return paged_attention_decode({query, heads * head_dim, heads * head_dim, head_dim, q_dtype, k_cache, v_cache,
+                                 block_table, context_lens, nullptr, k_scales, v_scales, out, batch, 1, heads,
+                                 kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                 max_context_len, sm_scale, codec, workspace, workspace_floats, stream});
 }
 
 KVECC_API int64_t kvecc_paged_attention_chunk_workspace(int64_t batch, int64_t q_len, int64_t heads,
@@ -1665,269 +1825,6 @@ KVECC_API int64_t kvecc_paged_attention_chunk_workspace(int64_t batch, int64_t q
   return rows * cdiv(max_context_len, chunk_finest_split(rows, max_context_len)) * (head_dim + 2);
 }
 
-}  // extern "C"
-
-// q_spans: null for kvecc_paged_attention_chunk, the device spans for the ragged entry (q_len its q_max).
-// Nothing but the kernels reads the spans: the launch geometry is the uniform call's.
-// interp: kvecc_paged_attention_interp -- Hamming(8,4) caches under 4 GiB through the interpolating
-// kernels at every q_len (q_len 1 included: the decode entry's kernels do not interpolate).
-static int paged_attention_chunk_impl(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
-                                      int64_t q_head_stride, int q_dtype, const void *k_cache,
-                                      const void *v_cache, const int32_t *block_table,
-                                      const int32_t *context_lens, const int32_t *q_spans,
-                                      const float *k_scales, const float *v_scales, void *out, int64_t batch,
-                                      int64_t q_len, int64_t heads, int64_t kv_heads, int64_t head_dim,
-                                      int64_t num_blocks, int64_t num_layers, int64_t layer,
-                                      int64_t block_size, int64_t max_blocks, int64_t max_context_len,
-                                      float sm_scale, int codec, float *workspace, int64_t workspace_floats,
-                                      void *stream, bool interp = false, uint64_t *stats = nullptr,
-                                      bool golay_stats = false, bool repair = false) {
-  if (batch < 0 || q_len < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
-  // golay_stats: kvecc_paged_attention_golay_stats, which has checked its codec and its buffer
-  // repair: kvecc_paged_attention_repair (stats non-null, hamming84: checked there), the counted call's
-  // geometry and argument values over the repairing kernels
-  if (stats && !golay_stats && codec != KVECC_CODEC_H84)
-    return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
-  if (interp && codec != KVECC_CODEC_H84)
-    return set_error(KVECC_EINVAL, "paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
-  if (batch == 0 || q_len == 0 || heads == 0) return KVECC_OK;
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_len > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: query strides (%lld, %lld, %lld) for head_dim %lld",
-                     (long long)q_batch_stride, (long long)q_token_stride, (long long)q_head_stride,
-                     (long long)head_dim);
-  // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
-  // (a ragged call stays here: the decode entry knows no spans)
-  if (!interp && !stats && !q_spans && q_len == 1 && (heads == 1 || q_head_stride == head_dim) &&
-      (batch == 1 || q_batch_stride == heads * head_dim))
-    return kvecc_paged_attention(query, q_dtype, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                 out, batch, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size,
-                                 max_blocks, max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
-  if (kv_heads < 1 || heads % kv_heads != 0)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld heads not a multiple of %lld kv heads",
-                     (long long)heads, (long long)kv_heads);
-  if (head_dim < 1 || head_dim > kAttnMaxD)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: head_dim %lld not in [1, %d]", (long long)head_dim,
-                     kAttnMaxD);
-  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
-      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL,
-                     "paged_attention_chunk: codec %d (int4, hamming74, hamming84, golay or golay_packed only)", codec);
-  // the byte family (kvecc.h): Hamming(8,4)'s layout, rules and launch geometry, its own kernels
-  const bool bytes = codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74;
-  const int table = codec;
-  if (bytes) codec = KVECC_CODEC_H84;
-  if (codec == KVECC_CODEC_H84 && head_dim % 4 != 0)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: %s head_dim must be a multiple of 4",
-                     table == KVECC_CODEC_NONE ? "int4" : table == KVECC_CODEC_H74 ? "hamming74" : "hamming84");
-  if (q_dtype != KVECC_F32 && q_dtype != KVECC_F16 && q_dtype != KVECC_BF16)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: bad dtype %d", q_dtype);
-  if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: bad cache geometry");
-  if (num_blocks < 1 || num_blocks * num_layers * kv_heads * block_size > 0x7FFFFFFFLL)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: cache rows must fit int32");
-  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
-  if (!query || !k_cache || !v_cache || !block_table || !context_lens || !k_scales || !v_scales ||
-      !out || !workspace)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: null pointer");
-  const int64_t vbatch = batch * q_len;  // query rows per head: the virtual batch
-  if (q_len > 0x7FFFFFFFLL || vbatch > 0x7FFFFFFFLL || vbatch * heads > 0x7FFFFFFFLL)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld x %lld x %lld query rows exceed the grid",
-                     (long long)batch, (long long)q_len, (long long)heads);
-  const int64_t need = kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, max_context_len);
-  if (workspace_floats < need)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: workspace %lld < %lld floats",
-                     (long long)workspace_floats, (long long)need);
-  ByteChunkArgs a;  // RaggedArgs for every other codec's kernels (the interpolating ones: a copy, below)
-  a.tab = (uint32_t)table;
-  a.q = query;
-  a.k_cache = k_cache;
-  a.v_cache = v_cache;
-  a.table = block_table;
-  a.ctx_lens = context_lens;
-  a.k_scales = k_scales;
-  a.v_scales = v_scales;
-  a.ws = workspace;
-  a.out = out;
-  a.heads = heads;
-  a.kv_heads = kv_heads;
-  a.d = head_dim;
-  a.g = codec == KVECC_CODEC_H84 ? head_dim / 4 : (head_dim + 2) / 3;
-  a.rowb = (uint32_t)KVECC_GOLAY_PACKED_ROW(a.g);
-  a.layers = num_layers;
-  a.layer = layer;
-  a.bs = block_size;
-  a.max_blocks = max_blocks;
-  a.ctx_cap = std::min(max_context_len, max_blocks * block_size);
-  a.sm_scale = sm_scale;
-  a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
-  a.q_len = (uint32_t)q_len;
-  a.vb0 = 0;
-  a.q_sb = q_batch_stride;
-  a.q_st = q_token_stride;
-  a.q_sh = q_head_stride;
-  a.cg_log2 = 0;
-  a.q_spans = q_spans;
-  int64_t tiles = 1;  // matrix-core chunk kernels: 16-column tiles per (sequence, head group)
-  const int64_t rows_total = num_blocks * num_layers * kv_heads * block_size;
-  const int64_t cb = rows_total * (codec == KVECC_CODEC_H84            ? head_dim
-                                   : codec == KVECC_CODEC_GOLAY_PACKED ? (int64_t)a.rowb
-                                                                       : 4 * a.g);
-  const bool fits = cb <= 0xFFFFFFFFLL && rows_total * 4 <= 0xFFFFFFFFLL;
-  a.cache_bytes = fits ? (uint32_t)cb : 0u;  // 0 selects the 64-bit-addressed kernels
-  a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
-  if (interp && !fits)
-    return set_error(KVECC_EINVAL, "paged_attention_interp: caches of 4 GiB or more are not supported");
-  if (stats && !fits)
-    return set_error(KVECC_EINVAL, "%s: caches of 4 GiB or more are not supported",
-                     golay_stats ? "paged_attention_golay_stats"
-                     : repair    ? "paged_attention_repair"
-                                 : "paged_attention_stats");
-  const int gq = attn_heads_per_wg(codec, head_dim, a.g, heads, kv_heads, fits);
-  // q_len 1 reaches here with a strided query only: the split kernels (and the decode entry's workspace bound);
-  // an interpolating call takes its matrix-core kernels at q_len 1 too (one tile, the same bound: `finest`)
-  // (a counted call takes its matrix-core kernels at every q_len too)
-  int gm = q_len > 1 || interp || stats ? attn_chunk_mfma_heads(codec, q_dtype, query, q_batch_stride, q_token_stride, q_head_stride,
-                                             head_dim, heads, kv_heads, fits)
-                     : 0;
-  // (a counted Golay decode step without GQA stays on the split kernels, as the decode entry's does: attn_mfma_heads)
-  if (golay_stats && q_len == 1 && heads == kv_heads) gm = 0;
-  int64_t wgs = 0;  // workgroups per split
-  if (gm) {
-    for (a.cg_log2 = 0; (1 << a.cg_log2) < gm; ++a.cg_log2) {}
-    tiles = cdiv(q_len, 16 / gm);
-    wgs = batch * (heads / gm) * tiles;
-    if (batch * (heads / gm) > kMaxGridY) gm = 0;  // the split kernels slice their grid
-  }
-  if (!gm) {
-    a.cg_log2 = 0;
-    wgs = vbatch * heads / gq;
-    if (heads / gq > kMaxGridY)
-      return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld heads exceed the grid", (long long)heads);
-  }
-  const int64_t finest = q_len > 1 ? chunk_finest_split(vbatch * heads, max_context_len)
-                                   : choose_split(std::max<int64_t>(1, batch * heads / 4), max_context_len);
-  a.split = std::max(choose_split(wgs, max_context_len,
-                                  !gm                        ? 4
-                                  : codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu
-                                                             : kMfmaWgPerCu),
-                     finest);
-  a.nsplit = cdiv(max_context_len, a.split);
-  if (a.nsplit > kMaxSplits)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: context %lld too long", (long long)max_context_len);
-  if (gm && a.nsplit * tiles > 0x7FFFFFFFLL)
-    return set_error(KVECC_EINVAL, "paged_attention_chunk: %lld splits x %lld tiles exceed the grid",
-                     (long long)a.nsplit, (long long)tiles);
-  a.par = a.cor = nullptr;
-  a.atab = a.atab_x = nullptr;
-  a.ctr = nullptr;
-  // the counted combine as in the decode entry: one query head per workgroup of the split kernels
-  if (!gm && gq == 1 && vbatch * heads <= kAttnCtrPerSlot) {
-    a.ctr = attn_counter_slot(stream);
-    if (!a.ctr) return KVECC_EHIP;
-  }
-  if (codec != KVECC_CODEC_H84) {
-    a.par = golay_parity_table_dev();
-    a.cor = golay_correct_table_dev();
-    a.atab = golay_attn_table_dev();
-    a.atab_x = golay_attn_x_table_dev();
-    if (!a.par || !a.cor || !a.atab || !a.atab_x) return KVECC_EHIP;
-  }
-  hipStream_t st = as_stream(stream);
-  int rc;
-  if (golay_stats) {  // the Golay counted kernels: StatsArgs too
-    StatsArgs sa;
-    static_cast<RaggedArgs &>(sa) = a;
-    sa.stats = stats;
-    if (gm) {
-      rc = launch_golay_mfma_stats(codec, sa, batch, tiles, st);
-    } else {
-      switch (q_dtype) {
-        case KVECC_F32: rc = launch_golay_stats_rows<float>(codec, sa, vbatch, gq, st); break;
-        case KVECC_F16: rc = launch_golay_stats_rows<__half>(codec, sa, vbatch, gq, st); break;
-        default: rc = launch_golay_stats_rows<__hip_bfloat16>(codec, sa, vbatch, gq, st); break;
-      }
-    }
-  } else if (repair) {  // the repairing kernels' argument blocks: the counted ones' values
-    RepairArgs ra;
-    RepairInterpArgs ri;
-    static_cast<RaggedArgs &>(ra) = a;
-    static_cast<RaggedArgs &>(ri) = a;
-    ra.stats = ri.stats = stats;
-    if (gm) {
-      rc = interp ? launch_mfma_stats(ri, batch, tiles, st) : launch_mfma_stats(ra, batch, tiles, st);
-    } else {
-      switch (q_dtype) {
-        case KVECC_F32:
-          rc = interp ? launch_h84_rows<float>(ri, vbatch, gq, st) : launch_h84_rows<float>(ra, vbatch, gq, st);
-          break;
-        case KVECC_F16:
-          rc = interp ? launch_h84_rows<__half>(ri, vbatch, gq, st) : launch_h84_rows<__half>(ra, vbatch, gq, st);
-          break;
-        default:
-          rc = interp ? launch_h84_rows<__hip_bfloat16>(ri, vbatch, gq, st)
-                      : launch_h84_rows<__hip_bfloat16>(ra, vbatch, gq, st);
-          break;
-      }
-    }
-  } else if (stats) {  // the counted kernels' argument blocks
-    StatsArgs sa;
-    StatsInterpArgs si;
-    static_cast<RaggedArgs &>(sa) = a;
-    static_cast<RaggedArgs &>(si) = a;
-    sa.stats = si.stats = stats;
-    if (gm) {
-      rc = interp ? launch_mfma_stats(si, batch, tiles, st) : launch_mfma_stats(sa, batch, tiles, st);
-    } else {
-      switch (q_dtype) {
-        case KVECC_F32:
-          rc = interp ? launch_h84_rows<float>(si, vbatch, gq, st) : launch_h84_rows<float>(sa, vbatch, gq, st);
-          break;
-        case KVECC_F16:
-          rc = interp ? launch_h84_rows<__half>(si, vbatch, gq, st) : launch_h84_rows<__half>(sa, vbatch, gq, st);
-          break;
-        default:
-          rc = interp ? launch_h84_rows<__hip_bfloat16>(si, vbatch, gq, st)
-                      : launch_h84_rows<__hip_bfloat16>(sa, vbatch, gq, st);
-          break;
-      }
-    }
-  } else if (interp) {
-    InterpArgs ia;  // the interpolating kernels' argument block
-    static_cast<RaggedArgs &>(ia) = a;
-    if (gm) {
-      rc = launch_mfma_interp(ia, batch, tiles, st);
-    } else {
-      switch (q_dtype) {
-        case KVECC_F32: rc = launch_h84_rows<float>(ia, vbatch, gq, st); break;
-        case KVECC_F16: rc = launch_h84_rows<__half>(ia, vbatch, gq, st); break;
-        default: rc = launch_h84_rows<__hip_bfloat16>(ia, vbatch, gq, st); break;
-      }
-    }
-  } else if (bytes && gm) {
-    rc = launch_byte_mfma_chunk(a, batch, tiles, st);
-  } else if (bytes) {
-    switch (q_dtype) {
-      case KVECC_F32: rc = launch_h84_rows<float>(a, vbatch, gq, st); break;
-      case KVECC_F16: rc = launch_h84_rows<__half>(a, vbatch, gq, st); break;
-      default: rc = launch_h84_rows<__hip_bfloat16>(a, vbatch, gq, st); break;
-    }
-  } else if (gm) {
-    rc = launch_mfma_chunk(codec, a, batch, tiles, st);
-  } else {
-    switch (q_dtype) {
-      case KVECC_F32: rc = launch_codec_rows<float>(codec, a, vbatch, gq, st); break;
-      case KVECC_F16: rc = launch_codec_rows<__half>(codec, a, vbatch, gq, st); break;
-      default: rc = launch_codec_rows<__hip_bfloat16>(codec, a, vbatch, gq, st); break;
-    }
-  }
-  if (rc != KVECC_OK) return rc;
-  return check_launch("paged_attention_chunk");
-}
-
-extern "C" {
-
 KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_stride,
                                           int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                           const void *k_cache, const void *v_cache,
@@ -1938,10 +1835,11 @@ KVECC_API int kvecc_paged_attention_chunk(const void *query, int64_t q_batch_str
                                           int64_t layer, int64_t block_size, int64_t max_blocks,
                                           int64_t max_context_len, float sm_scale, int codec,
                                           float *workspace, int64_t workspace_floats, void *stream) {
-  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, nullptr, k_scales, v_scales, out, batch, q_len, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, nullptr, k_scales, v_scales, out, batch, q_len, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    {});
 }
 
 KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_batch_stride,
@@ -1956,10 +1854,11 @@ KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_ba
                                                  int64_t max_context_len, float sm_scale, int codec,
                                                  float *workspace, int64_t workspace_floats, void *stream) {
   if (!q_spans) return set_error(KVECC_EINVAL, "paged_attention_chunk_ragged: null q_spans");
-  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream);
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    {});
 }
 
 KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
@@ -1972,10 +1871,11 @@ KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_st
                                            int64_t layer, int64_t block_size, int64_t max_blocks,
                                            int64_t max_context_len, float sm_scale, int codec,
                                            float *workspace, int64_t workspace_floats, void *stream) {
-  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream, true);
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    {AttnKind::plain, true});
 }
 
 KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
@@ -1992,11 +1892,11 @@ KVECC_API int kvecc_paged_attention_stats(const void *query, int64_t q_batch_str
   if (!stats) return set_error(KVECC_EINVAL, "paged_attention_stats: null stats");
   if (codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
-  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream,
-                                    interp != 0, stats);
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    {AttnKind::counted, interp != 0, stats});
 }
 
 KVECC_API int kvecc_paged_attention_repair(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
@@ -2012,11 +1912,11 @@ KVECC_API int kvecc_paged_attention_repair(const void *query, int64_t q_batch_st
   if (!stats) return set_error(KVECC_EINVAL, "paged_attention_repair: null stats");
   if (codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_repair: codec %d (the repairing kernels need hamming84)", codec);
-  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream,
-                                    interp != 0, stats, false, true);
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    {AttnKind::repair, interp != 0, stats});
 }
 
 KVECC_API int kvecc_paged_attention_golay_stats(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
@@ -2034,11 +1934,11 @@ KVECC_API int kvecc_paged_attention_golay_stats(const void *query, int64_t q_bat
   if (codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
     return set_error(KVECC_EINVAL, "paged_attention_golay_stats: codec %d (these counted kernels need golay or golay_packed)",
                      codec);
-  return paged_attention_chunk_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, workspace, workspace_floats, stream, false,
-                                    stats, true);
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    {AttnKind::golay_counted, false, stats});
 }
 
 }  // extern "C"

@@ -634,11 +634,44 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
     return out
 
 
+def _host_stats_ptr(stats, n):
+    """The pointer of a host stats buffer of >= n words (2: new_stats, 3: new_scrub_stats)."""
+    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
+            or stats.numel() < n or stats.device.type != "cpu"):
+        maker = "new_stats" if n == 2 else "new_scrub_stats"
+        raise ValueError(f"stats must be a contiguous int64 host tensor of >= {n} elements (cpu_ops.{maker}), got "
+                         f"{getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
+                         f"on {getattr(stats, 'device', None)}")
+    return _ptr(stats)
+
+
+def _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                      layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats, stats_min,
+                      codec_checks=()):
+    """Host twin of ops._call_chunk_entry: the same checks in the same order, a host
+    stats buffer of >= stats_min words, and the call of kvecc_cpu_paged_attention_<entry>."""
+    from .ops import _check_attention_chunk_args, _check_q_spans, _chunk_entry_args
+    _check_cpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    for check in codec_checks:
+        check(codec)
+    sp = _host_stats_ptr(stats, stats_min) if stats is not None else None
+    if q_spans is not None:
+        _check_q_spans(q_spans, query.shape[0], query.device)
+    _lib.call("kvecc_cpu_paged_attention_" + entry,
+              *_chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, layer_idx, block_size, sm_scale, codec, int(max_context_len or 0), q_spans,
+                                 interp, sp),
+              NUM_THREADS)
+    return out
+
+
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
                                interp=False, stats=None, repair=False):
     """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
-    from .ops import _check_attention_chunk_args, _check_interp_codec, _check_q_spans, _check_stats_codec
+    from .ops import _check_interp_codec, _check_stats_codec
     if repair:
         if stats is None:
             raise ValueError("repair=True needs stats= (a host int64 buffer of >= 3 elements): the repairing "
@@ -646,54 +679,12 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
         return paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                            out, layer_idx, block_size, sm_scale, codec, stats,
                                            max_context_len=max_context_len, q_spans=q_spans, interp=interp)
-    _check_cpu(query, "Query")
-    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                out, block_size, codec)
-    if interp:
-        _check_interp_codec(codec)
-    batch, q_len, heads, head_dim = query.shape
-    num_blocks, num_layers, kv_heads, _ = k_cache.shape
-    max_blocks = block_table.shape[1]
-    if stats is not None:  # kvecc_cpu_paged_attention_stats: the totals go to words 0 and 1
-        _check_stats_codec(codec)
-        if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
-                or stats.numel() < 2 or stats.device.type != "cpu"):
-            raise ValueError("stats must be a contiguous int64 host tensor of >= 2 elements (cpu_ops.new_stats), got "
-                             f"{getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
-                             f"on {getattr(stats, 'device', None)}")
-        sp = _ptr(stats)
-        if q_spans is not None:
-            _check_q_spans(q_spans, batch, query.device)
-        _lib.call("kvecc_cpu_paged_attention_stats", _ptr(query), query.stride(0), query.stride(1),
-                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-                  int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), sp,
-                  NUM_THREADS)
-        return out
-    if interp:
-        if q_spans is not None:
-            _check_q_spans(q_spans, batch, query.device)
-        _lib.call("kvecc_cpu_paged_attention_interp", _ptr(query), query.stride(0), query.stride(1),
-                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-                  int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
-        return out
-    if q_spans is not None:
-        _check_q_spans(q_spans, batch, query.device)
-        _lib.call("kvecc_cpu_paged_attention_chunk_ragged", _ptr(query), query.stride(0), query.stride(1),
-                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-                  int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
-        return out
-    _lib.call("kvecc_cpu_paged_attention_chunk", _ptr(query), query.stride(0), query.stride(1),
-              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-              _ptr(context_lens), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads,
-              head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-              int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], NUM_THREADS)
-    return out
+    checks = ([_check_interp_codec] if interp else []) + ([_check_stats_codec] if stats is not None else [])
+    entry = ("stats" if stats is not None else "interp" if interp else
+             "chunk_ragged" if q_spans is not None else "chunk")
+    return _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                             layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats, 2,
+                             checks)
 
 
 def paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
@@ -703,37 +694,19 @@ def paged_attention_repair_into(query, k_cache, v_cache, block_table, context_le
     same arguments, checks and rules; k_cache / v_cache are written in place and
     ``stats`` is a host int64 [>= 3] (new_scrub_stats): words 0 / 1 the counted
     twin's, word 2 += bytes rewritten."""
-    from .ops import _check_attention_chunk_args, _check_q_spans, _check_repair_codec
+    from .ops import _check_repair_codec
     _check_repair_codec(codec)
     if stats is None:
         raise ValueError("paged_attention_repair_into needs a stats buffer (cpu_ops.new_scrub_stats)")
-    _check_cpu(query, "Query")
-    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                out, block_size, codec)
-    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
-            or stats.numel() < 3 or stats.device.type != "cpu"):
-        raise ValueError("stats must be a contiguous int64 host tensor of >= 3 elements (cpu_ops.new_scrub_stats), "
-                         f"got {getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
-                         f"on {getattr(stats, 'device', None)}")
-    batch, q_len, heads, head_dim = query.shape
-    num_blocks, num_layers, kv_heads, _ = k_cache.shape
-    max_blocks = block_table.shape[1]
-    if q_spans is not None:
-        _check_q_spans(q_spans, batch, query.device)
-    _lib.call("kvecc_cpu_paged_attention_repair", _ptr(query), query.stride(0), query.stride(1),
-              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-              int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), _ptr(stats),
-              NUM_THREADS)
-    return out
+    return _call_chunk_entry("repair", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                             layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats, 3)
 
 
 def paged_attention_counted_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, layer_idx, block_size, sm_scale, codec, stats, max_context_len=0,
                                  q_spans=None, interp=False):
     """Host twin of ops.paged_attention_counted_into (same arguments and checks)."""
-    from .ops import _check_attention_chunk_args, _check_counted_codec, _check_q_spans
+    from .ops import _check_counted_codec
     _check_counted_codec(codec, interp)
     if stats is None:
         raise ValueError("paged_attention_counted_into needs a stats buffer (cpu_ops.new_stats)")
@@ -742,25 +715,8 @@ def paged_attention_counted_into(query, k_cache, v_cache, block_table, context_l
                                           out, layer_idx, block_size, sm_scale, codec,
                                           max_context_len=max_context_len, q_spans=q_spans, interp=interp,
                                           stats=stats)
-    _check_cpu(query, "Query")
-    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                out, block_size, codec)
-    if (not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or not stats.is_contiguous()
-            or stats.numel() < 2 or stats.device.type != "cpu"):
-        raise ValueError("stats must be a contiguous int64 host tensor of >= 2 elements (cpu_ops.new_stats), got "
-                         f"{getattr(stats, 'dtype', type(stats))} {tuple(getattr(stats, 'shape', ()))} "
-                         f"on {getattr(stats, 'device', None)}")
-    batch, q_len, heads, head_dim = query.shape
-    num_blocks, num_layers, kv_heads, _ = k_cache.shape
-    max_blocks = block_table.shape[1]
-    if q_spans is not None:
-        _check_q_spans(q_spans, batch, query.device)
-    _lib.call("kvecc_cpu_paged_attention_golay_stats", _ptr(query), query.stride(0), query.stride(1),
-              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-              int(max_context_len or 0), float(sm_scale), SHIM_CODECS[codec], _ptr(stats), NUM_THREADS)
-    return out
+    return _call_chunk_entry("golay_stats", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                             out, layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats, 2)
 
 
 def paged_attention_counted(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,

@@ -1238,6 +1238,62 @@ def _check_stats_codec(codec):
         raise ValueError(f"stats needs hamming84 (the counted attention kernels), got codec {codec!r}")
 
 
+# The chunk-family entries (kvecc_paged_attention_<entry>, and the host twins
+# kvecc_cpu_paged_attention_<entry>) share one argument list; these are the
+# arguments an entry adds to kvecc_paged_attention_chunk's: (q_spans, the interp
+# flag, stats)
+_CHUNK_ENTRY_EXTRAS = {"chunk": (False, False, False), "chunk_ragged": (True, False, False),
+                       "interp": (True, False, False), "stats": (True, True, True),
+                       "repair": (True, True, True), "golay_stats": (True, False, True)}
+
+
+def _chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                      layer_idx, block_size, sm_scale, codec, mcl, q_spans, interp, sp):
+    """A chunk-family entry's arguments up to its workspace (the GPU entries) or
+    its thread count (the host twins); sp: the stats pointer."""
+    takes_spans, takes_interp, takes_stats = _CHUNK_ENTRY_EXTRAS[entry]
+    batch, q_len, heads, head_dim = query.shape
+    num_blocks, num_layers, kv_heads, _ = k_cache.shape
+    args = [_ptr(query), query.stride(0), query.stride(1), query.stride(2), _DT[query.dtype], _ptr(k_cache),
+            _ptr(v_cache), _ptr(block_table), _ptr(context_lens)]
+    if takes_spans:
+        args.append(_ptr(q_spans))
+    args += [_ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads, head_dim, num_blocks,
+             num_layers, int(layer_idx), int(block_size), block_table.shape[1], mcl, float(sm_scale),
+             SHIM_CODECS[codec]]
+    if takes_interp:
+        args.append(int(bool(interp)))
+    if takes_stats:
+        args.append(sp)
+    return args
+
+
+def _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                      layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats,
+                      codec_checks=()):
+    """The shared work of the chunk-family entries: the argument checks (then the
+    caller's codec_checks, each called with the codec), the stats pointer, the
+    spans, the cached workspace, and the call of kvecc_paged_attention_<entry>."""
+    _check_gpu(query, "Query")
+    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, block_size, codec)
+    for check in codec_checks:
+        check(codec)
+    sp = _sptr(stats, query.device) if stats is not None else None
+    batch, q_len, heads, head_dim = query.shape
+    if q_spans is not None:
+        _check_q_spans(q_spans, batch, query.device)
+    max_blocks = block_table.shape[1]
+    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
+    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
+    ws = _attn_workspace(query.device, ws_n)
+    _lib.call("kvecc_paged_attention_" + entry,
+              *_chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, layer_idx, block_size, sm_scale, codec, mcl, q_spans, interp, sp),
+              _ptr(ws), ws.numel(), _stream(query.device))
+    return out
+
+
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
                                interp=False, stats=None, repair=False):
@@ -1278,51 +1334,12 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
         return paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                            out, layer_idx, block_size, sm_scale, codec, stats,
                                            max_context_len=max_context_len, q_spans=q_spans, interp=interp)
-    _check_gpu(query, "Query")
-    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                out, block_size, codec)
-    if interp:
-        _check_interp_codec(codec)
-    sp = None
-    if stats is not None:
-        _check_stats_codec(codec)
-        sp = _sptr(stats, query.device)
-    batch, q_len, heads, head_dim = query.shape
-    if q_spans is not None:
-        _check_q_spans(q_spans, batch, query.device)
-    num_blocks, num_layers, kv_heads, _ = k_cache.shape
-    max_blocks = block_table.shape[1]
-    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
-    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
-    ws = _attn_workspace(query.device, ws_n)
-    if sp is not None:
-        _lib.call("kvecc_paged_attention_stats", _ptr(query), query.stride(0), query.stride(1),
-                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-                  mcl, float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), sp, _ptr(ws), ws.numel(),
-                  _stream(query.device))
-        return out
-    if interp:
-        _lib.call("kvecc_paged_attention_interp", _ptr(query), query.stride(0), query.stride(1),
-                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-                  mcl, float(sm_scale), SHIM_CODECS[codec], _ptr(ws), ws.numel(), _stream(query.device))
-        return out
-    if q_spans is not None:
-        _lib.call("kvecc_paged_attention_chunk_ragged", _ptr(query), query.stride(0), query.stride(1),
-                  query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-                  _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-                  heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-                  mcl, float(sm_scale), SHIM_CODECS[codec], _ptr(ws), ws.numel(), _stream(query.device))
-        return out
-    _lib.call("kvecc_paged_attention_chunk", _ptr(query), query.stride(0), query.stride(1), query.stride(2),
-              _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table), _ptr(context_lens),
-              _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len, heads, kv_heads, head_dim, num_blocks,
-              num_layers, int(layer_idx), int(block_size), max_blocks, mcl, float(sm_scale),
-              SHIM_CODECS[codec], _ptr(ws), ws.numel(), _stream(query.device))
-    return out
+    checks = ([_check_interp_codec] if interp else []) + ([_check_stats_codec] if stats is not None else [])
+    entry = ("stats" if stats is not None else "interp" if interp else
+             "chunk_ragged" if q_spans is not None else "chunk")
+    return _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                             layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats,
+                             checks)
 
 
 def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
@@ -1369,25 +1386,8 @@ def paged_attention_repair_into(query, k_cache, v_cache, block_table, context_le
     _check_repair_codec(codec)
     if stats is None:
         raise ValueError("paged_attention_repair_into needs a stats buffer (ops.new_stats)")
-    _check_gpu(query, "Query")
-    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                out, block_size, codec)
-    sp = _sptr(stats, query.device)
-    batch, q_len, heads, head_dim = query.shape
-    if q_spans is not None:
-        _check_q_spans(q_spans, batch, query.device)
-    num_blocks, num_layers, kv_heads, _ = k_cache.shape
-    max_blocks = block_table.shape[1]
-    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
-    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
-    ws = _attn_workspace(query.device, ws_n)
-    _lib.call("kvecc_paged_attention_repair", _ptr(query), query.stride(0), query.stride(1),
-              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-              mcl, float(sm_scale), SHIM_CODECS[codec], int(bool(interp)), sp, _ptr(ws), ws.numel(),
-              _stream(query.device))
-    return out
+    return _call_chunk_entry("repair", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
+                             layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats)
 
 
 _GOLAY_CODECS = ("golay", "golay_packed")
@@ -1424,24 +1424,8 @@ def paged_attention_counted_into(query, k_cache, v_cache, block_table, context_l
                                           out, layer_idx, block_size, sm_scale, codec,
                                           max_context_len=max_context_len, q_spans=q_spans, interp=interp,
                                           stats=stats)
-    _check_gpu(query, "Query")
-    _check_attention_chunk_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                out, block_size, codec)
-    sp = _sptr(stats, query.device)
-    batch, q_len, heads, head_dim = query.shape
-    if q_spans is not None:
-        _check_q_spans(q_spans, batch, query.device)
-    num_blocks, num_layers, kv_heads, _ = k_cache.shape
-    max_blocks = block_table.shape[1]
-    mcl = int(max_context_len) if max_context_len and max_context_len > 0 else max_blocks * block_size
-    ws_n = _lib.load().kvecc_paged_attention_chunk_workspace(batch, q_len, heads, head_dim, mcl)
-    ws = _attn_workspace(query.device, ws_n)
-    _lib.call("kvecc_paged_attention_golay_stats", _ptr(query), query.stride(0), query.stride(1),
-              query.stride(2), _DT[query.dtype], _ptr(k_cache), _ptr(v_cache), _ptr(block_table),
-              _ptr(context_lens), _ptr(q_spans), _ptr(k_scales), _ptr(v_scales), _ptr(out), batch, q_len,
-              heads, kv_heads, head_dim, num_blocks, num_layers, int(layer_idx), int(block_size), max_blocks,
-              mcl, float(sm_scale), SHIM_CODECS[codec], sp, _ptr(ws), ws.numel(), _stream(query.device))
-    return out
+    return _call_chunk_entry("golay_stats", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                             out, layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats)
 
 
 def paged_attention_counted(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
