@@ -423,6 +423,22 @@ KVECC_API int kvecc_shim_read_batch(const void *k_cache, const void *v_cache, co
  * attention_ecc.py:342,391-423), 0 for Golay (reference_attention_ecc).  Query head h reads cache head h / (heads / kv_heads).  `workspace`:
  * kvecc_paged_attention_workspace(...) floats.  head_dim <= 256.
  *
+ * Scale range (every attention entry of this header, device and host).  Scales
+ * are non-negative finite floats; a scale of exactly 0 (an unwritten slot of a
+ * zeroed cache) gives its token the value 0, and a sequence whose V scales are all
+ * 0 returns exactly 0.  The accuracy of the output relative to the largest
+ * v_scale of a sequence does not depend on that scale's magnitude anywhere
+ * between 2^-100 and 2^100: the matrix-core kernels (fp16 queries) carry
+ * p * v_scale to the matrix cores divided by a running power of two, kept in the
+ * online-softmax state and clamped to [2^-100, 2^100], and every other kernel
+ * works in fp32 throughout.  What bounds a call is its output type, not the
+ * kernels: an output above the largest finite value of q_dtype is +-inf and one
+ * below its smallest subnormal is 0 (fp16: 65504 and 2^-24, so v_scales between
+ * about 2^-12 and 2^13 keep fp16 outputs normal and finite).  Weights below 2^-100
+ * lose precision gradually, far below anything an output type can hold.
+ * k_scales enter the scores only, in fp32.  Negative, infinite and NaN scales are
+ * undefined (the writers never produce them).
+ *
  * Byte caches without SECDED (no reference counterpart: the reference attends
  * over Hamming(8,4) and Golay only).  kvecc_paged_attention,
  * kvecc_paged_attention_chunk, kvecc_paged_attention_chunk_ragged and their

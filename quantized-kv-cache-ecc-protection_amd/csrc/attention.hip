@@ -827,6 +827,22 @@ constexpr int kMfmaStep = 32;  // tokens per wave step
 // 0x6400 and one v_pk_add_f16 of -1032 per pair measured within noise.)
 constexpr float kMfmaValScale = 16777216.0f;  // 2^24
 constexpr float kMfmaValOffset = 8.0f;
+// The PV operand's normaliser (kvecc.h "Scale range").  The weights w = p * v_scale go
+// to the matrix cores as an f16 hi + lo pair, which carries 22 bits only while w is far
+// above the f16 subnormal step 2^-24 and below 65504; v_scales are absmax / 7 of the
+// activations and bounded by neither.  So each column keeps a power of two c, the
+// accumulator holds O / c and the operand is w / c < 2: c is the power of two at or below
+// max(c * alpha, the step's largest w), rescaled like l and psum, clamped to 2^+-100 so
+// that c, 1 / c and c * 2^24 stay normal floats.  Multiplying by a power of two is exact;
+// psum never sees c.
+__device__ __forceinline__ float pv_norm_pow2(float x) {
+  const float y = fminf(fmaxf(x, 0x1p-100f), 0x1p100f);
+  return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, y) & 0x7F800000u);
+}
+// 1 / c of a normal power of two c in [2^-126, 2^126]
+__device__ __forceinline__ float pv_norm_recip(float c) {
+  return __builtin_bit_cast(float, 0x7F000000u - __builtin_bit_cast(uint32_t, c));
+}
 // two table values (data nibbles 0..15) -> f16 operand pair, lo in bits 0..15
 __device__ __forceinline__ uint32_t nib_pair_f16(uint32_t lo, uint32_t hi) {
   return __builtin_amdgcn_perm(hi, lo, 0x0c040c00u);  // [0, hi, 0, lo]

@@ -134,6 +134,7 @@
   for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   float m = -INFINITY, l = 0.0f;
   float psum = 0.0f;  // sum of p * v_scale over this lane's tokens (the offset fold)
+  float pvc = 0.0f;   // the PV normaliser ([normaliser]); 0: nothing accumulated yet
   const float qoff = kMfmaValOffset * qsum;
 
   // the cache rows of token i's neighbours, positions max(l - 1, 0) and min(l + 1, n_b - 1)
@@ -303,15 +304,29 @@
     m = mn;
     l *= alpha;
     psum *= alpha;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] *= alpha;
-    uint32_t phi[4], plo[4];
+    float pw[8], wmax = 0.0f;  // p * v_scale
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       const float p0 = attn_exp(s[2 * h] - mu), p1 = attn_exp(s[2 * h + 1] - mu);
       l += p0 + p1;
-      const float w0 = p0 * vs[2 * h], w1 = p1 * vs[2 * h + 1];
-      psum += w0 + w1;
+      pw[2 * h] = p0 * vs[2 * h];
+      pw[2 * h + 1] = p1 * vs[2 * h + 1];
+      psum += pw[2 * h] + pw[2 * h + 1];
+      wmax = fmaxf(wmax, fmaxf(pw[2 * h], pw[2 * h + 1]));
+    }
+    // [normaliser] pv_norm_pow2 (attention.hip): one power of two per column, uniform over its
+    // four lanes as m is; acc holds O / pvc, the operand is pw / pvc < 2 whatever v_scale is
+    wmax = fmaxf(wmax, __shfl_xor(wmax, 16, kWave));
+    wmax = fmaxf(wmax, __shfl_xor(wmax, 32, kWave));
+    const float ca = pvc * alpha;
+    pvc = pv_norm_pow2(fmaxf(ca, wmax));
+    const float cinv = pv_norm_recip(pvc), beta = ca * cinv;  // alpha, and the old O / pvc in the new pvc (<= 2)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] *= beta;
+    uint32_t phi[4], plo[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const float w0 = pw[2 * h] * cinv, w1 = pw[2 * h + 1] * cinv;
       const auto hi = __builtin_amdgcn_cvt_pkrtz(w0, w1);
       const auto lo = __builtin_amdgcn_cvt_pkrtz(w0 - (float)hi[0], w1 - (float)hi[1]);
       phi[h] = __builtin_bit_cast(uint32_t, hi);
@@ -339,7 +354,7 @@
   l += __shfl_xor(l, 32, kWave);
   psum += __shfl_xor(psum, 16, kWave);
   psum += __shfl_xor(psum, 32, kWave);
-  const float poff = kMfmaValOffset * psum;
+  const float poff = kMfmaValOffset * psum, oscale = pvc * kMfmaValScale;
   if (n < G) {
     if (g == 0) {
       gml[0][wave][n] = m;
@@ -348,7 +363,7 @@
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][n][MT * (4 * g + r) + mt] = acc[mt][r] * kMfmaValScale - poff;
+      for (int r = 0; r < 4; ++r) red[wave][n][MT * (4 * g + r) + mt] = acc[mt][r] * oscale - poff;
   }
   __syncthreads();
   for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {

@@ -1127,9 +1127,11 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
           decode_row(k_cache, srow, k_scales[srow], codewords(k_cache, sl), codewords(k_cache, sr));
         else
           decode_row(k_cache, srow, k_scales[srow]);
-        float sc = 0.0f;
-        for (int64_t j = 0; j < head_dim; ++j) sc += q[j] * kv[j];
-        sc *= sm_scale;
+        // the dot product in double: a serial fp32 sum's error grows with |k_scale| and the
+        // softmax sees it absolutely (tests/test_attention_scale_range.py, the kk = +6 rungs)
+        double dot = 0.0;
+        for (int64_t j = 0; j < head_dim; ++j) dot += (double)q[j] * (double)kv[j];
+        const float sc = (float)(dot * (double)sm_scale);
         const float mn = std::max(m, sc);
         const float alpha = m == -INFINITY ? 0.0f : std::exp(m - mn);
         const float beta = std::exp(sc - mn);
