@@ -974,12 +974,14 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_ragged_kernel(R
 #undef ATTN_BODY_CHUNK
 }
 // the interpolating entry's: the ragged form with double errors interpolated
-// from the neighbouring tokens before the operands are built (a body of its own)
+// from the neighbouring tokens before the operands are built (the body's [interpolation] islands)
 template <int D>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_interp_kernel(InterpArgs a) {
   constexpr int G = 16;
   using ChunkMap = ChunkMapT<RaggedArgs>;
-#include "attn_h84_mfma_interp_body.inc"
+#define ATTN_BODY_CHUNK 2
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
 }
 // the counted entry's (kvecc_paged_attention_stats): the ragged form and the interpolating
 // form with the [statistics] islands
@@ -987,9 +989,11 @@ template <int D>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_stats_interp_kernel(StatsInterpArgs a) {
   constexpr int G = 16;
   using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 2
 #define ATTN_BODY_STATS 1
-#include "attn_h84_mfma_interp_body.inc"
+#include "attn_h84_mfma_body.inc"
 #undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
 }
 template <int D>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_stats_kernel(StatsArgs a) {
@@ -1007,11 +1011,13 @@ template <int D>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_repair_interp_kernel(RepairInterpArgs a) {
   constexpr int G = 16;
   using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 2
 #define ATTN_BODY_STATS 1
 #define ATTN_BODY_REPAIR 1
-#include "attn_h84_mfma_interp_body.inc"
+#include "attn_h84_mfma_body.inc"
 #undef ATTN_BODY_REPAIR
 #undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
 }
 template <int D>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_repair_kernel(RepairArgs a) {

@@ -1,66 +1,65 @@
-// Body of paged_attn_h84_mfma_kernel (ATTN_BODY_CHUNK 0, `a` an AttnArgs, G query
-// heads in the first G columns) and of paged_attn_h84_mfma_chunk_kernel (ATTN_BODY_CHUNK
-// 1, `a` a ChunkArgs, G = 16 (token, head) columns: ChunkMap; the ragged entry's
-// paged_attn_h84_mfma_ragged_kernel is the same text over a RaggedArgs and its ChunkMap), included by
-// attention.hip inside each kernel: the decode kernel's text is what it always
-// was, so its code is too (see ChunkArgs).
-// attention.hip defines ATTN_BODY_CHUNK around each inclusion; it is no build switch.
-// The counted kernel (paged_attn_h84_mfma_stats_kernel, `a` a StatsArgs, the ragged form) also
-// defines ATTN_BODY_STATS: the [statistics] islands; without it the preprocessed text is what it was.
-// The repairing kernel (paged_attn_h84_mfma_repair_kernel, `a` a RepairArgs) defines ATTN_BODY_REPAIR
-// as well: the [repair] islands, in which the counting workgroup stores the corrected codewords back
-// where it counts them (kvecc.h "Repairing attention"); without it the text is the counted kernel's.
+// Body of the Hamming(8,4) matrix-core kernels, included by attention.hip inside each kernel, which
+// defines ATTN_BODY_CHUNK (and the island switches below) around the inclusion; they are no build
+// switches.  A kernel's code follows from its preprocessed text alone, so a form whose text an edit
+// leaves alone keeps its code (see ChunkArgs).
+//   ATTN_BODY_CHUNK 0  paged_attn_h84_mfma_kernel: `a` an AttnArgs, G query heads in the first G columns.
+//   ATTN_BODY_CHUNK 1  paged_attn_h84_mfma_chunk_kernel: `a` a ChunkArgs, G = 16 (token, head) columns
+//     (ChunkMap); the ragged entry's paged_attn_h84_mfma_ragged_kernel is the same text over a
+//     RaggedArgs and its ChunkMap.  The byte family's three kernels (paged_attn_byte_mfma_*) are
+//     forms 0 and 1 over their argument blocks: only the decode table differs.
+//   ATTN_BODY_CHUNK 2  paged_attn_h84_mfma_interp_kernel: `a` an InterpArgs, the ragged form with the
+//     [interpolation] islands (kvecc.h "Interpolated attention"), as attn_split_body.inc has them:
+//     * rows[] gains a halo: rows[kHalo + i] is R(i), the cache row of position t0 + i of the
+//       sequence for i in [-1, npad] (attn_mfma_rows.inc); kHalo is 0 in the other forms.
+//     * the first look: h84_double4 of every loaded dword (the syndrome / parity SWAR of the
+//       scrubber's h84_dirty4 and four more operations) marks its type-2 bytes.  A lane none of
+//       whose words of a K row (of four V rows) holds one goes on as the chunk kernel does.
+//     * the slow path, per lane and per operand: the same bytes of rows l - 1 and l + 1 (clamped to
+//       [0, n_b - 1]; a -1 block reads as zero codewords) come through the same buffer descriptor,
+//       every byte is decoded, doubles become interp_word(q, L, R, type), and the word is
+//       re-encoded (h84_interp_fix4) -- so the corrected nibbles reach nib_pair_f16 through the
+//       same table as every other byte.  The neighbour loads of one K row (of four V rows) are
+//       issued together, one round trip; only the words that hold a double are rewritten.
+// ATTN_BODY_STATS (paged_attn_h84_mfma_stats_kernel, `a` a StatsArgs; _stats_interp_kernel, a
+// StatsInterpArgs): the [statistics] islands, which count the words of load_step -- every stored
+// byte once -- and never the neighbour words of the slow path.
+// ATTN_BODY_REPAIR as well (paged_attn_h84_mfma_repair_kernel, a RepairArgs; _repair_interp_kernel, a
+// RepairInterpArgs): the [repair] islands, in which the counting workgroup stores the corrected
+// codewords back where it counts them (kvecc.h "Repairing attention"), before the slow path
+// rewrites any in registers -- a double is never stored, and the neighbour words the slow path
+// loads decode to the same nibbles before and after any store.
+// Shared with attn_golay_mfma_body.inc, one copy each: attn_mfma_columns.inc, attn_mfma_rows.inc,
+// attn_mfma_descriptors.inc, attn_mfma_softmax.inc, attn_mfma_merge.inc (their headers say what they read
+// and define).
   constexpr int KK = D / 32;  // QK MFMAs per 16-token tile
   constexpr int MT = D / 16;  // PV M-tiles; V bytes per lane per token
   constexpr int KB = D / 4;   // K bytes per lane per token
   constexpr int VW = MT >= 4 ? MT / 4 : 1;  // V dwords per token
   constexpr int kWaves = kBlock / kWave;
+#if ATTN_BODY_CHUNK == 2  // [interpolation] the halo: 4 keeps the 16-byte reads of load_step aligned
+  constexpr int kHalo = 4;
+  constexpr uint32_t kVMask = MT >= 4 ? 0xFFFFFFFFu : (1u << (8 * MT)) - 1u;  // the bytes a V load fills
+  __shared__ __attribute__((aligned(16))) int32_t rows[kHalo + kMaxSplit + kMfmaStep + 4];
+  __shared__ int32_t blks[kMaxSplit + 3];
+#else
+  constexpr int kHalo = 0;
   __shared__ __attribute__((aligned(16))) int32_t rows[kMaxSplit + kMfmaStep];
   __shared__ int32_t blks[kMaxSplit + 1];
+#endif
   __shared__ uint8_t lut[256];
   __shared__ float red[kWaves][G][D];
   __shared__ float gml[2][kWaves][G];
 
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const int n = lane & 15, g = lane >> 4;
-#if ATTN_BODY_CHUNK  // [column map] cm is used by every other chunk island of this file
-  const ChunkMap cm(a, n);  // column n's (token, head); blockIdx.x = tile * nsplit + split
-  if constexpr (ChunkMap::kRagged) {
-    if (!cm.any) {  // every token of the tile is padding: nothing staged, no table or cache read
-      cm.put_empty(a);
-      return;
-    }
-  }
-  const int64_t b = cm.b, h0 = cm.h0;
-  const int64_t hk = h0 / (a.heads / a.kv_heads);
-#ifdef ATTN_BODY_STATS  // [statistics] who counts (kvecc.h "Counted attention"): uniform per workgroup
-  // The tile that holds the sequence's last valid token, in the first column group of
-  // its cache head, counts: one workgroup per (sequence, cache head, split).  It walks
-  // the sequence's n_b rows -- the tile's largest key limit unless the span overruns
-  // q_max; the columns' own limits mask the scores either way ([score mask]).
-  const ChunkSpan csp(a, b);
-  const bool counts = csp.v1(a) > csp.v0() && cm.tile == (uint32_t)(csp.v1(a) - 1) / (16u >> a.cg_log2) &&
-                      h0 % (a.heads / a.kv_heads) == 0;
-  const int64_t ctx = counts ? min<int64_t>(a.ctx_lens[b], a.ctx_cap) : cm.ctx;
+#include "attn_mfma_columns.inc"
+#ifdef ATTN_BODY_STATS  // [statistics] this lane's counters
   uint32_t n_single = 0, n_double = 0;
 #ifdef ATTN_BODY_REPAIR  // [repair] bytes rewritten: the statistics buffer's word 2
   uint32_t n_rewritten = 0;
 #endif
-#else
-  const int64_t ctx = cm.ctx;  // the largest key limit of the tile's columns
 #endif
-  const int64_t t0 = (int64_t)cm.split_idx * a.split;
-#else
-  const int64_t hgroups = a.heads / G;
-  const int64_t b = blockIdx.y / hgroups, h0 = (blockIdx.y % hgroups) * G;
-  const int64_t hk = h0 / (a.heads / a.kv_heads);
-  const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);
-  const int64_t t0 = (int64_t)blockIdx.x * a.split;
-#endif
-  const int64_t t1 = min<int64_t>(t0 + a.split, ctx);
-  const int ntok = t1 > t0 ? (int)(t1 - t0) : 0;
-#if ATTN_BODY_CHUNK  // [key limit] applied at [score mask]
-  const int col_lim = cm.col_limit(t0);  // this column's keys: the split's tokens below it
+#if ATTN_BODY_CHUNK == 2  // [interpolation] the sequence's length n_b: what neighbours clamp to
+  // (shim_read's ctx for this sequence alone)
+  const int64_t nb = max<int64_t>(min<int64_t>(a.ctx_lens[b], a.ctx_cap), 0);
 #endif
   // Q^T operand (B): column n = head h0 + n, k-slot 8g + j of MFMA kk = d (D/4)g + 8kk + j.
   // Issued first: it lands during the block-table round trip instead of
@@ -78,50 +77,10 @@
 #endif
     qop[kk] = __builtin_bit_cast(f16x8, v);
   }
-  {  // block-table slice -> cache rows (-1: no block / past the split)
-    const uint32_t bs = (uint32_t)a.bs;
-    const uint32_t lb0 = (uint32_t)(t0 / a.bs);
-    // the whole split's slice, bounded by the table rather than the context, so
-    // the load does not wait for context_lens (one dependent HBM trip fewer)
-    const int64_t tmax = min<int64_t>(t0 + a.split, a.max_blocks * a.bs);
-    const int nlb = tmax > t0 ? (int)((uint32_t)(tmax - 1) / bs - lb0 + 1) : 0;
-    const int32_t *tab = a.table + b * a.max_blocks + lb0;
-    for (int j = threadIdx.x; j < nlb; j += kBlock) blks[j] = tab[j];
-    __syncthreads();
-    const int32_t head_row0 = (int32_t)((a.layer * a.kv_heads + hk) * a.bs);
-    const int32_t blk_rows = (int32_t)(a.layers * a.kv_heads * a.bs);
-    const int npad = (ntok + kMfmaStep - 1) / kMfmaStep * kMfmaStep;
-    for (int i = threadIdx.x; i < npad; i += kBlock) {
-      int32_t row = -1;
-      if (i < ntok) {
-        const uint32_t pos = (uint32_t)(t0 + i);
-        const uint32_t lb = pos / bs;
-        const int32_t blk = blks[lb - lb0];
-        if (blk >= 0) row = blk * blk_rows + head_row0 + (int32_t)(pos - lb * bs);
-      }
-      rows[i] = row;
-    }
-  }
+#include "attn_mfma_rows.inc"
   // kBlock == 256: one table entry per thread (the byte family's kernels: their codec's table)
   lut[threadIdx.x] = (uint8_t)byte_table_nibble(a, threadIdx.x);
-  float qsum = 0.0f;  // sum of head n's query over all d (the offset fold)
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qsum += (float)qop[kk][e];
-  qsum += __shfl_xor(qsum, 16, kWave);
-  qsum += __shfl_xor(qsum, 32, kWave);
-  __syncthreads();
-
-  const __amdgpu_buffer_rsrc_t krs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.k_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.v_cache), 0, (int)a.cache_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t ksrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.k_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t vsrs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.v_scales), 0, (int)a.scale_bytes, kRsrcWord3);
-  const float qscale = a.sm_scale * kAttnLogScale;
+#include "attn_mfma_descriptors.inc"
   f32x4 acc[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -130,6 +89,11 @@
   float pvc = 0.0f;   // the PV normaliser ([normaliser]); 0: nothing accumulated yet
   const float qoff = kMfmaValOffset * qsum;
 
+#if ATTN_BODY_CHUNK == 2  // [interpolation] the cache rows of token i's neighbours, positions
+  // max(l - 1, 0) and min(l + 1, n_b - 1)
+  auto left_of = [&](int i) { return rows[kHalo + (t0 + i > 0 ? i - 1 : i)]; };
+  auto right_of = [&](int i) { return rows[kHalo + (t0 + i + 1 < nb ? i + 1 : i)]; };
+#endif
   // one step's operands in registers: 2 K rows (tokens i0 + n, i0 + 16 + n),
   // 8 V rows and scales (tokens i0 + 16(j >> 2) + 4g + (j & 3)); invalid rows
   // read row 0 and are masked
@@ -140,13 +104,13 @@
     float ks[8], vs[8];
   };
   auto load_step = [&](int i0, Step &st) {
-    const int4 r0 = *reinterpret_cast<const int4 *>(&rows[i0 + 4 * g]);
-    const int4 r1 = *reinterpret_cast<const int4 *>(&rows[i0 + 16 + 4 * g]);
+    const int4 r0 = *reinterpret_cast<const int4 *>(&rows[kHalo + i0 + 4 * g]);
+    const int4 r1 = *reinterpret_cast<const int4 *>(&rows[kHalo + i0 + 16 + 4 * g]);
     st.rv[0] = r0.x; st.rv[1] = r0.y; st.rv[2] = r0.z; st.rv[3] = r0.w;
     st.rv[4] = r1.x; st.rv[5] = r1.y; st.rv[6] = r1.z; st.rv[7] = r1.w;
 #pragma unroll
     for (int tau = 0; tau < 2; ++tau) {
-      const int32_t r = rows[i0 + 16 * tau + n];
+      const int32_t r = rows[kHalo + i0 + 16 * tau + n];
       load_chunk<KB>(krs, (uint32_t)max(r, 0) * (uint32_t)D + (uint32_t)(KB * g), st.kw[tau]);
     }
 #pragma unroll
@@ -171,7 +135,7 @@
     if (counts) {
 #pragma unroll
       for (int tau = 0; tau < 2; ++tau) {
-        const int32_t r = rows[i0 + 16 * tau + n];
+        const int32_t r = rows[kHalo + i0 + 16 * tau + n];
         uint32_t dirty = 0;
 #pragma unroll
         for (int k = 0; k < KB / 4; ++k) dirty |= h_code4(kw[tau][k]);
@@ -201,7 +165,7 @@
     if (counts) {
 #pragma unroll
       for (int tau = 0; tau < 2; ++tau) {
-        if (rows[i0 + 16 * tau + n] >= 0) {  // not a -1 block's / a past row's row 0
+        if (rows[kHalo + i0 + 16 * tau + n] >= 0) {  // not a -1 block's / a past row's row 0
 #pragma unroll
           for (int k = 0; k < KB / 4; ++k) h84_count4(kw[tau][k], n_single, n_double);
         }
@@ -213,6 +177,55 @@
           for (int k = 0; k < VW; ++k)  // (head_dim 32: two bytes per token, the rest of the dword as clean codewords)
             h84_count4(MT < 4 ? vw[j][k] & ((1u << (8 * (MT & 3))) - 1u) : vw[j][k], n_single, n_double);
         }
+      }
+    }
+#endif
+#if ATTN_BODY_CHUNK == 2  // [interpolation] the first look, then the slow path in the lanes that hold a double,
+    // after the islands above have seen the stored words.  One K row, or four V rows, at
+    // a time: their neighbour words are what the slow path keeps in registers, and
+    // with all ten rows' at once the kernel took 225-256 VGPRs (2 waves per SIMD) for 140
+#pragma unroll
+    for (int tau = 0; tau < 2; ++tau) {
+      uint32_t kd = 0;
+#pragma unroll
+      for (int k = 0; k < KB / 4; ++k) kd |= h84_double4(kw[tau][k]);
+      if (kd) {
+        uint32_t wl[KB / 4], wr[KB / 4];
+        const int i = i0 + 16 * tau + n;
+        const int32_t rl = left_of(i), rr = right_of(i);
+        load_chunk<KB>(krs, (uint32_t)max(rl, 0) * (uint32_t)D + (uint32_t)(KB * g), wl);
+        load_chunk<KB>(krs, (uint32_t)max(rr, 0) * (uint32_t)D + (uint32_t)(KB * g), wr);
+#pragma unroll
+        for (int k = 0; k < KB / 4; ++k)
+          if (h84_double4(kw[tau][k]))  // the words without a double stay as they are
+            kw[tau][k] = h84_interp_fix4(kw[tau][k], rl >= 0 ? wl[k] : 0u, rr >= 0 ? wr[k] : 0u);
+      }
+    }
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      uint32_t vd = 0;
+#pragma unroll
+      for (int j = 4 * half; j < 4 * half + 4; ++j)
+#pragma unroll
+        for (int k = 0; k < VW; ++k) vd |= h84_double4(vw[j][k] & kVMask);
+      if (vd) {
+        uint32_t wl[4][VW], wr[4][VW];
+        int32_t rl[4], rr[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int i = i0 + 16 * half + 4 * g + jj;  // token of row j = 4 half + jj
+          rl[jj] = left_of(i);
+          rr[jj] = right_of(i);
+          load_chunk<MT>(vrs, (uint32_t)max(rl[jj], 0) * (uint32_t)D + (uint32_t)(MT * n), wl[jj]);
+          load_chunk<MT>(vrs, (uint32_t)max(rr[jj], 0) * (uint32_t)D + (uint32_t)(MT * n), wr[jj]);
+        }
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+          for (int k = 0; k < VW; ++k)
+            if (h84_double4(vw[4 * half + jj][k] & kVMask))
+              vw[4 * half + jj][k] = h84_interp_fix4(vw[4 * half + jj][k], rl[jj] >= 0 ? wl[jj][k] : 0u,
+                                                     rr[jj] >= 0 ? wr[jj][k] : 0u);
       }
     }
 #endif
@@ -235,56 +248,7 @@
       }
     }
     // ---- online softmax over this lane's 8 tokens of head n
-    float s[8];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#if ATTN_BODY_CHUNK  // [score mask] col_lim from [key limit]
-      const bool seen = i0 + 16 * (j >> 2) + 4 * g + (j & 3) < col_lim;
-      s[j] = rv[j] >= 0 && seen ? (S[j >> 2][j & 3] * kMfmaValScale - qoff) * (qscale * ks[j]) : -INFINITY;
-#else
-      s[j] = rv[j] >= 0 ? (S[j >> 2][j & 3] * kMfmaValScale - qoff) * (qscale * ks[j]) : -INFINITY;
-#endif
-      mx = fmaxf(mx, s[j]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, kWave));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
-    const float mn = fmaxf(m, mx);
-    const float mu = mn == -INFINITY ? 0.0f : mn;  // no valid token yet: nothing to scale
-    const float alpha = attn_exp(m - mu);
-    m = mn;
-    l *= alpha;
-    psum *= alpha;
-    float pw[8], wmax = 0.0f;  // p * v_scale
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float p0 = attn_exp(s[2 * h] - mu), p1 = attn_exp(s[2 * h + 1] - mu);
-      l += p0 + p1;
-      pw[2 * h] = p0 * vs[2 * h];
-      pw[2 * h + 1] = p1 * vs[2 * h + 1];
-      psum += pw[2 * h] + pw[2 * h + 1];
-      wmax = fmaxf(wmax, fmaxf(pw[2 * h], pw[2 * h + 1]));
-    }
-    // [normaliser] pv_norm_pow2 (attention.hip): one power of two per column, uniform over its
-    // four lanes as m is; acc holds O / pvc, the operand is pw / pvc < 2 whatever v_scale is
-    wmax = fmaxf(wmax, __shfl_xor(wmax, 16, kWave));
-    wmax = fmaxf(wmax, __shfl_xor(wmax, 32, kWave));
-    const float ca = pvc * alpha;
-    pvc = pv_norm_pow2(fmaxf(ca, wmax));
-    const float cinv = pv_norm_recip(pvc), beta = ca * cinv;  // alpha, and the old O / pvc in the new pvc (<= 2)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] *= beta;
-    uint32_t phi[4], plo[4];
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float w0 = pw[2 * h] * cinv, w1 = pw[2 * h + 1] * cinv;
-      const auto hi = __builtin_amdgcn_cvt_pkrtz(w0, w1);
-      const auto lo = __builtin_amdgcn_cvt_pkrtz(w0 - (float)hi[0], w1 - (float)hi[1]);
-      phi[h] = __builtin_bit_cast(uint32_t, hi);
-      plo[h] = __builtin_bit_cast(uint32_t, lo);
-    }
-    const f16x8 pb_hi = __builtin_bit_cast(f16x8, u32x4{phi[0], phi[1], phi[2], phi[3]});
-    const f16x8 pb_lo = __builtin_bit_cast(f16x8, u32x4{plo[0], plo[1], plo[2], plo[3]});
+#include "attn_mfma_softmax.inc"
     // ---- O^T += V^T . P: M-tile mt takes byte mt of each token's chunk
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -301,54 +265,7 @@
   }
 
   // ---- merge: the 4 lanes of a head, then the workgroup's waves
-  l += __shfl_xor(l, 16, kWave);
-  l += __shfl_xor(l, 32, kWave);
-  psum += __shfl_xor(psum, 16, kWave);
-  psum += __shfl_xor(psum, 32, kWave);
-  const float poff = kMfmaValOffset * psum, oscale = pvc * kMfmaValScale;
-  if (n < G) {
-    if (g == 0) {
-      gml[0][wave][n] = m;
-      gml[1][wave][n] = l;
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][n][MT * (4 * g + r) + mt] = acc[mt][r] * oscale - poff;
-  }
-  __syncthreads();
-#if !ATTN_BODY_CHUNK  // [merge: workspace row] decode: head h0's row, the others at a fixed stride (below)
-  const int64_t ws_stride = a.nsplit * (a.d + 2);
-  float *ws0 = a.ws + ((b * a.heads + h0) * a.nsplit + blockIdx.x) * (a.d + 2);
-#endif
-  for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
-    const int h = idx / D, d = idx % D;
-#if ATTN_BODY_CHUNK  // [merge: workspace row] chunk: column h's own output row; none: a column past the chunk
-    const int64_t orow = cm.out_row(a, h);
-    if (orow < 0) continue;
-#endif
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) M = fmaxf(M, gml[0][w][h]);
-    float o = 0.0f, L = 0.0f;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const float mw = gml[0][w][h];
-      const float wt = mw == -INFINITY ? 0.0f : attn_exp(mw - M);
-      o += red[w][h][d] * wt;
-      L += gml[1][w][h] * wt;
-    }
-#if ATTN_BODY_CHUNK  // [merge: workspace row] orow from the loop's head / ws0 from before the loop
-    float *ws = a.ws + (orow * a.nsplit + cm.split_idx) * (a.d + 2);
-#else
-    float *ws = ws0 + h * ws_stride;
-#endif
-    ws_put(ws + 2 + d, o);
-    if (d == 0) {
-      ws_put(ws, M);
-      ws_put(ws + 1, L);
-    }
-  }
+#include "attn_mfma_merge.inc"
 #ifdef ATTN_BODY_STATS  // [statistics] one reduction and at most two atomics per counting workgroup
   if (counts) {
 #ifdef ATTN_BODY_REPAIR  // [repair] ... and a third for the bytes rewritten
