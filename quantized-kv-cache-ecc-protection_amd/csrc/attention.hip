@@ -1505,24 +1505,7 @@ static int64_t chunk_finest_split(int64_t rows, int64_t max_context_len) {
 }
 
 // ---- the entries' shared front half ----------------------------------------------
-// A call's parameters, in the order and under the names of kvecc.h's chunk-family
-// entries (the decode entry: q_len 1, no spans, its strides unused).
-struct AttnCall {
-  const void *query;
-  int64_t q_sb, q_st, q_sh;
-  int q_dtype;
-  const void *k_cache, *v_cache;
-  const int32_t *block_table, *context_lens, *q_spans;
-  const float *k_scales, *v_scales;
-  void *out;
-  int64_t batch, q_len, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks;
-  int64_t max_context_len;
-  float sm_scale;
-  int codec;
-  float *workspace;
-  int64_t workspace_floats;
-  void *stream;
-};
+// (AttnCall, the record of a call, and AttnMode are in kvecc_internal.h: the host twin takes them too)
 
 // What an entry decides between the argument fill and the split count (attn_setup's
 // `plan`, which also sets a.split and, in a chunked call, a.cg_log2)
@@ -1687,24 +1670,6 @@ static int paged_attention_decode(const AttnCall &c) {
 }
 
 // ---- chunked causal attention ---------------------------------------------------
-// Which chunk-family entry a call came through.  q_spans (AttnCall) is null for
-// kvecc_paged_attention_chunk and the device spans for the ragged entry (q_len its
-// q_max); nothing but the kernels reads the spans: the launch geometry is the
-// uniform call's.
-enum class AttnKind {
-  plain,          // kvecc_paged_attention_chunk / _chunk_ragged / _interp
-  counted,        // kvecc_paged_attention_stats: Hamming(8,4), stats[0..1]
-  golay_counted,  // kvecc_paged_attention_golay_stats: golay / golay_packed, no interpolation
-  repair,         // kvecc_paged_attention_repair: the counted call's geometry and argument values
-                  // over the repairing kernels, stats[2] too
-};
-struct AttnMode {
-  AttnKind kind = AttnKind::plain;
-  // Hamming(8,4) caches under 4 GiB through the interpolating kernels at every q_len (q_len 1
-  // included: the decode entry's kernels do not interpolate)
-  bool interp = false;
-  uint64_t *stats = nullptr;  // the library's sharded statistics buffer: every kind but plain
-};
 static const char *mode_entry(const AttnMode &m) {
   switch (m.kind) {
     case AttnKind::golay_counted: return "paged_attention_golay_stats";

@@ -91,6 +91,42 @@ void store_y(void *y, int dtype, int64_t i, float v) {
 
 bool bad(int64_t n) { return n < 0; }
 
+// the host Golay tables, built on first use: parity[4096], then correct[4096]
+// (kvecc_internal.h); the encoders take the first half only
+const uint16_t *host_golay_tables() {
+  static const struct Tables {
+    uint16_t t[8192];
+    Tables() {
+      build_golay_parity_table(t);
+      build_golay_correct_table(t + 4096);
+    }
+  } tables;
+  return tables.t;
+}
+
+// Golay word k of cache row `row` (g words a row): 3 little-endian bytes of a
+// packed row, or the int32 word (bits 24-31 as stored: golay_decode1 ignores them)
+inline uint32_t golay_word(const void *cache, bool packed, int64_t row, int64_t g, int64_t k) {
+  if (!packed) return (uint32_t)reinterpret_cast<const int32_t *>(cache)[row * g + k];
+  const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + row * KVECC_GOLAY_PACKED_ROW(g) + 3 * k;
+  return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+}
+
+// sequence b's query span (kvecc.h "Query spans"); no spans: the uniform call's (0, q_len)
+struct Span {
+  int64_t first, count;
+};
+inline Span span_of(const int32_t *q_spans, int64_t b, int64_t q_len) {
+  return q_spans ? Span{q_spans[3 * b], q_spans[3 * b + 1]} : Span{0, q_len};
+}
+
+// row index of position `pos` of cache head h in physical block blk, in a
+// [blocks, layers, kv_heads, block_size] cache (rows of codewords, and the scales)
+inline int64_t cache_slot(int64_t blk, int64_t layers, int64_t layer, int64_t kv_heads, int64_t h,
+                          int64_t block_size, int64_t pos) {
+  return ((blk * layers + layer) * kv_heads + h) * block_size + pos % block_size;
+}
+
 }  // namespace
 }  // namespace kvecc
 
@@ -168,9 +204,7 @@ KVECC_API int kvecc_cpu_hamming84_decode(const uint8_t *cw, uint8_t *data, uint8
 KVECC_API int kvecc_cpu_golay_encode(const uint8_t *trip, int32_t *cw, int64_t m, int threads) {
   if (bad(m)) return set_error(KVECC_EINVAL, "cpu_golay_encode: negative m");
   if (m && (!trip || !cw)) return set_error(KVECC_EINVAL, "cpu_golay_encode: null pointer");
-  static uint16_t par[4096];
-  static bool ready = [] { build_golay_parity_table(par); return true; }();
-  (void)ready;
+  const uint16_t *par = host_golay_tables();
   parallel_for(m, threads, 64, [&](int64_t b, int64_t e, int) {
     for (int64_t i = b; i < e; ++i) {
       uint32_t d = golay_pack(trip[3 * i], trip[3 * i + 1], trip[3 * i + 2]);
@@ -184,13 +218,7 @@ KVECC_API int kvecc_cpu_golay_decode(const int32_t *cw, uint8_t *trip, uint8_t *
                                      uint64_t *stats, int threads) {
   if (bad(m)) return set_error(KVECC_EINVAL, "cpu_golay_decode: negative m");
   if (m && (!trip || !cw)) return set_error(KVECC_EINVAL, "cpu_golay_decode: null pointer");
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
+  const uint16_t *tab = host_golay_tables();
   std::vector<Acc2> acc(std::max(1, clamp_threads(threads, m, 1 << 16)));
   parallel_for(m, threads, 64, [&](int64_t b, int64_t e, int t) {
     uint64_t bits = 0, unc = 0;
@@ -215,9 +243,7 @@ KVECC_API int kvecc_cpu_golay_encode_rows(const uint8_t *nibbles, int32_t *cw, i
                                           int64_t d, int threads) {
   if (rows < 0 || d < 0) return set_error(KVECC_EINVAL, "cpu_golay_encode_rows: negative size");
   if (rows && d && (!nibbles || !cw)) return set_error(KVECC_EINVAL, "cpu_golay_encode_rows: null pointer");
-  static uint16_t par[4096];
-  static bool ready = [] { build_golay_parity_table(par); return true; }();
-  (void)ready;
+  const uint16_t *par = host_golay_tables();
   const int64_t g = (d + 2) / 3;
   parallel_for(rows, threads, 1, [&](int64_t b, int64_t e, int) {
     for (int64_t r = b; r < e; ++r)
@@ -235,13 +261,7 @@ KVECC_API int kvecc_cpu_golay_decode_rows(const int32_t *cw, uint8_t *nibbles, i
                                           int64_t d, uint64_t *stats, int threads) {
   if (rows < 0 || d < 0) return set_error(KVECC_EINVAL, "cpu_golay_decode_rows: negative size");
   if (rows && d && (!nibbles || !cw)) return set_error(KVECC_EINVAL, "cpu_golay_decode_rows: null pointer");
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
+  const uint16_t *tab = host_golay_tables();
   const int64_t g = (d + 2) / 3;
   std::vector<Acc2> acc(std::max(1, clamp_threads(threads, rows, 1)));
   parallel_for(rows, threads, 1, [&](int64_t b, int64_t e, int t) {
@@ -271,9 +291,7 @@ KVECC_API int kvecc_cpu_golay_encode_packed(const uint8_t *nibbles, uint8_t *cod
                                             int threads) {
   if (m < 0) return set_error(KVECC_EINVAL, "cpu_golay_encode_packed: negative m");
   if (m && (!nibbles || !codewords)) return set_error(KVECC_EINVAL, "cpu_golay_encode_packed: null pointer");
-  static uint16_t par[4096];
-  static bool ready = [] { build_golay_parity_table(par); return true; }();
-  (void)ready;
+  const uint16_t *par = host_golay_tables();
   parallel_for((m + 7) / 8, threads, 1, [&](int64_t b, int64_t e, int) {
     for (int64_t g = b; g < e; ++g)
       for (int64_t k = 8 * g; k < m && k < 8 * g + 8; ++k) {
@@ -296,13 +314,7 @@ KVECC_API int kvecc_cpu_golay_decode_packed(const uint8_t *codewords, uint8_t *n
                                             int threads) {
   if (m < 0) return set_error(KVECC_EINVAL, "cpu_golay_decode_packed: negative m");
   if (m && (!nibbles || !codewords)) return set_error(KVECC_EINVAL, "cpu_golay_decode_packed: null pointer");
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
+  const uint16_t *tab = host_golay_tables();
   const int64_t groups = (m + 7) / 8;
   std::vector<Acc2> acc(std::max(1, clamp_threads(threads, groups, 1 << 10)));
   parallel_for(groups, threads, 1, [&](int64_t b, int64_t e, int t) {
@@ -694,9 +706,7 @@ KVECC_API int kvecc_cpu_shim_write(const void *k, const void *v, int x_dtype, in
       const int64_t rr = item - side * per_side;
       const int64_t pos = rr / hkv, h = rr - pos * hkv;
       const int64_t r = (batch - 1) * per_side + rr;  // only the last batch is stored
-      const int64_t slot =
-          (((int64_t)block_table[pos / block_size] * num_layers + layer) * hkv + h) * block_size +
-          pos % block_size;
+      const int64_t slot = cache_slot(block_table[pos / block_size], num_layers, layer, hkv, h, block_size, pos);
       rows.store(side, r, slot, nib);
     }
   });
@@ -733,7 +743,7 @@ KVECC_API int kvecc_cpu_shim_append(const void *k, const void *v, int x_dtype, i
       if (lb >= table_stride) continue;
       const int64_t blk = block_table[b * table_stride + lb];
       if (blk < 0) continue;
-      rows.store(side, r, ((blk * num_layers + layer) * hkv + h) * block_size + p % block_size, nib);
+      rows.store(side, r, cache_slot(blk, num_layers, layer, hkv, h, block_size, p), nib);
     }
   });
   return KVECC_OK;
@@ -768,7 +778,8 @@ KVECC_API int kvecc_cpu_shim_append_ragged(const void *k, const void *v, int x_d
       const int64_t r = item - side * per_side;  // (b * q_max + t) * hkv + h: the input row
       const int64_t bt = r / hkv, h = r - bt * hkv;
       const int64_t b = bt / q_max, t = bt - b * q_max;
-      const int64_t first = q_spans[3 * b], count = q_spans[3 * b + 1], base = q_spans[3 * b + 2];
+      const auto [first, count] = span_of(q_spans, b, q_max);
+      const int64_t base = q_spans[3 * b + 2];
       if (first < 0 || t < first || t >= std::min(first + count, q_max)) continue;  // padding
       const int64_t ri = (base + t - first) * hkv + h;  // dense over the valid tokens
       if (start_pos[b] < 0) continue;
@@ -776,7 +787,7 @@ KVECC_API int kvecc_cpu_shim_append_ragged(const void *k, const void *v, int x_d
       if (lb >= table_stride) continue;
       const int64_t blk = block_table[b * table_stride + lb];
       if (blk < 0) continue;
-      rows.store(side, r, ri, ((blk * num_layers + layer) * hkv + h) * block_size + p % block_size, nib);
+      rows.store(side, r, ri, cache_slot(blk, num_layers, layer, hkv, h, block_size, p), nib);
     }
   });
   return KVECC_OK;
@@ -799,19 +810,12 @@ KVECC_API int kvecc_cpu_shim_read(const void *k_cache, const void *v_cache, cons
     return set_error(KVECC_EINVAL, "cpu_shim_read: bad cache geometry");
   if (!k_cache || !v_cache || !k_scales || !v_scales || !block_table || !k_out || !v_out)
     return set_error(KVECC_EINVAL, "cpu_shim_read: null pointer");
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
+  const uint16_t *tab = host_golay_tables();
   const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
   const bool golay = codec == KVECC_CODEC_GOLAY || packed;
   const int64_t g = golay ? (d + 2) / 3 : d;
   auto slot_of = [&](int64_t l, int64_t h) {
-    return (((int64_t)block_table[l / block_size] * num_layers + layer) * hkv + h) * block_size +
-           l % block_size;
+    return cache_slot(block_table[l / block_size], num_layers, layer, hkv, h, block_size, l);
   };
   const int64_t per_side = hkv * ctx;
   const std::vector<uint8_t> zero_row(golay ? 0 : (size_t)d, 0);  // a missing block's codewords
@@ -834,14 +838,8 @@ KVECC_API int kvecc_cpu_shim_read(const void *k_cache, const void *v_cache, cons
       if (golay) {
         const void *cache = side ? v_cache : k_cache;
         for (int64_t q = 0; q < g; ++q) {
-          uint32_t cnt, w;
-          if (packed) {
-            const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + slot * KVECC_GOLAY_PACKED_ROW(g) + 3 * q;
-            w = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
-          } else {
-            w = (uint32_t)reinterpret_cast<const int32_t *>(cache)[slot * g + q];
-          }
-          const uint32_t dw = golay_decode1(w, tab, tab + 4096, cnt);
+          uint32_t cnt;
+          const uint32_t dw = golay_decode1(golay_word(cache, packed, slot, g, q), tab, tab + 4096, cnt);
           bits += cnt & 3u;
           unc += cnt >> 2;
           for (int64_t u = 0; u < 3 && 3 * q + u < d; ++u)
@@ -933,13 +931,7 @@ KVECC_API int kvecc_cpu_cache_scrub(void *k_cache, void *v_cache, const int32_t 
   if (table_stride > 0x7FFFFFFFLL || block_size > 0x7FFFFFFFLL || table_stride * block_size > 0x7FFFFFFFLL ||
       batch > 0x7FFFFFFFLL || layer_count > 0x7FFFFFFFLL)
     return set_error(KVECC_EINVAL, "cpu_cache_scrub: sizes exceed 32-bit indexing");
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
+  const uint16_t *tab = host_golay_tables();
   const int64_t g = golay ? (d + 2) / 3 : d;
   const int64_t rowb = packed ? KVECC_GOLAY_PACKED_ROW(g) : golay ? 4 * g : d;
   int64_t bound = table_stride * block_size;
@@ -962,16 +954,16 @@ KVECC_API int kvecc_cpu_cache_scrub(void *k_cache, void *v_cache, const int32_t 
       if (nv <= 0) continue;
       const int64_t blk = block_table[b * table_stride + lb];
       if (blk < 0 || blk >= num_blocks) continue;
-      uint8_t *base = reinterpret_cast<uint8_t *>(side ? v_cache : k_cache) +
-                      ((blk * num_layers + layer_first + li) * hkv) * block_size * rowb;
       for (int64_t h = 0; h < hkv; ++h) {
-        uint8_t *run = base + h * block_size * rowb;
+        // the block's rows of this head: row 0 of the run is position 0's slot
+        const int64_t row0 = cache_slot(blk, num_layers, layer_first + li, hkv, h, block_size, 0);
+        uint8_t *run = reinterpret_cast<uint8_t *>(side ? v_cache : k_cache) + row0 * rowb;
         c0 = c1 = rew = 0;
         if (packed) {
           for (int64_t r = 0; r < nv; ++r)
             for (int64_t k = 0; k < g; ++k) {
               uint8_t *c = run + r * rowb + 3 * k;
-              const uint32_t w = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
+              const uint32_t w = golay_word(run, true, r, g, k);
               const uint32_t x = golay_scrub1(w, tab, tab + 4096, c0, c1, rew);
               if (x) {  // whole bytes of the canonical word: a second writer of a shared block stores the same
                 c[0] = (uint8_t)(w ^ x);
@@ -1002,52 +994,63 @@ KVECC_API int kvecc_cpu_cache_scrub(void *k_cache, void *v_cache, const int32_t 
   return KVECC_OK;
 }
 
-// ---- paged decode attention (host twin of attention.hip) ---------------------
-// The reference's order exactly: one (b, h) at a time, tokens in order, online
-// softmax in fp32 (attention_ecc.py:355-427).  No valid token: Hamming(8,4)
+}  // extern "C"
+
+// ---- paged attention (host twin of attention.hip) ----------------------------
+namespace kvecc {
+namespace {
+
+// Every (sequence, position, cache head, K|V row) a counting call counts, in
+// that order, as fn(cache, row): the first n_b positions -- context_lens[b]
+// clamped by max_context_len and by max_blocks * block_size -- of each sequence
+// that has a valid query token (an all-padding span is not read), -1 blocks
+// skipped; once per cache head, whatever the query rows and heads that look at it.
+template <class F>
+void for_each_counted_row(const AttnCall &c, F fn) {
+  const int64_t mcl = c.max_context_len > 0 ? c.max_context_len : c.max_blocks * c.block_size;
+  for (int64_t b = 0; b < c.batch; ++b) {
+    const auto [first, count] = span_of(c.q_spans, b, c.q_len);
+    if (first < 0 || count <= 0 || first >= c.q_len) continue;
+    const int64_t nb = std::min<int64_t>(std::min<int64_t>(c.context_lens[b], mcl), c.max_blocks * c.block_size);
+    for (int64_t pos = 0; pos < nb; ++pos) {
+      const int32_t blk = c.block_table[b * c.max_blocks + pos / c.block_size];
+      if (blk < 0) continue;
+      for (int64_t hk = 0; hk < c.kv_heads; ++hk) {
+        const int64_t row = cache_slot(blk, c.num_layers, c.layer, c.kv_heads, hk, c.block_size, pos);
+        fn(c.k_cache, row);
+        fn(c.v_cache, row);
+      }
+    }
+  }
+}
+
+// The rows of a validated call, in the reference's order exactly: one (b, t, h) at
+// a time, tokens in order, online softmax in fp32 (attention_ecc.py:355-427).  No valid token: Hamming(8,4)
 // -8.0 per lane (the reference kernel's -1e20 masking, :342,391-423), Golay 0
-// (reference_attention_ecc, :806-807,885-886).
-// One body for both entries: query row (b, t, h) at b*q_sb + t*q_st + h*q_sh
-// (elements), at position context_lens[b] - q_len + t, attending to the keys at
-// or before it; q_len 1 is the decode entry.  q_spans (ragged entry, kvecc.h
-// "Query spans"): row b's (first, count) replace (0, q_len).
-static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int64_t q_sh, int q_dtype,
-                              const void *k_cache, const void *v_cache, const int32_t *block_table,
-                              const int32_t *context_lens, const float *k_scales, const float *v_scales,
-                              void *out, int64_t batch, int64_t q_len, int64_t heads, int64_t kv_heads,
-                              int64_t head_dim, int64_t num_blocks, int64_t num_layers, int64_t layer,
-                              int64_t block_size, int64_t max_blocks, int64_t max_context_len,
-                              float sm_scale, int codec, int threads, const int32_t *q_spans = nullptr,
-                              bool interp = false) {
-  if (batch < 0 || heads < 0 || kv_heads < 0 || head_dim < 0)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: negative size");
-  if (interp && codec != KVECC_CODEC_H84)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
-  if (batch == 0 || heads == 0 || q_len == 0) return KVECC_OK;
-  if (kv_heads < 1 || heads % kv_heads != 0)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: heads not a multiple of kv heads");
-  if (head_dim < 1) return set_error(KVECC_EINVAL, "cpu_paged_attention: empty head_dim");
-  if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
-      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL,
-                     "cpu_paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed only)", codec);
-  if ((codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74) && head_dim % 4 != 0)  // as the device entries
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: %s head_dim must be a multiple of 4",
-                     codec == KVECC_CODEC_NONE ? "int4" : "hamming74");
-  if (q_dtype < KVECC_F32 || q_dtype > KVECC_BF16)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: bad dtype %d", q_dtype);
-  if (num_layers < 1 || layer < 0 || layer >= num_layers || block_size < 1 || max_blocks < 1)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: bad cache geometry");
-  if (!query || !k_cache || !v_cache || !block_table || !context_lens || !k_scales || !v_scales || !out)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention: null pointer");
-  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
+// (reference_attention_ecc, :806-807,885-886).  Query row (b, t, h) is at
+// b*q_sb + t*q_st + h*q_sh (elements), at position context_lens[b] - q_len + t,
+// attending to the keys at or before it; q_len 1 is the decode entry.  q_spans
+// (kvecc.h "Query spans"): row b's (first, count) replace (0, q_len).  An
+// interpolating call sends every stored byte through h84_decode4 and doubles
+// through interp_word of the neighbouring tokens (clamped to the sequence).
+// INTERP is a template argument so that the byte loop of a call that does not interpolate
+// carries no neighbour test (with the flag read in the loop a plain Hamming(8,4) call
+// takes over twice as long); the results are the same bits either way.
+template <bool INTERP>
+void attention_rows(const AttnCall &c, int threads) {
+  // hot fields into locals: the row loop reads no record
+  const void *const query = c.query, *const k_cache = c.k_cache, *const v_cache = c.v_cache;
+  const int64_t q_sb = c.q_sb, q_st = c.q_st, q_sh = c.q_sh;
+  const int q_dtype = c.q_dtype, codec = c.codec;
+  const int32_t *const block_table = c.block_table, *const context_lens = c.context_lens, *const q_spans = c.q_spans;
+  const float *const k_scales = c.k_scales, *const v_scales = c.v_scales;
+  void *const out = c.out;
+  const int64_t batch = c.batch, q_len = c.q_len, heads = c.heads, kv_heads = c.kv_heads, head_dim = c.head_dim;
+  const int64_t num_layers = c.num_layers, layer = c.layer, block_size = c.block_size, max_blocks = c.max_blocks;
+  const float sm_scale = c.sm_scale;
+  constexpr bool interp = INTERP;
+  const int64_t max_context_len = c.max_context_len > 0 ? c.max_context_len : max_blocks * block_size;
+  const uint16_t *tab = host_golay_tables();
   const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
   const bool golay = codec == KVECC_CODEC_GOLAY || packed;
   const int64_t g = golay ? (head_dim + 2) / 3 : head_dim;
@@ -1060,14 +1063,8 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
                           const uint8_t *cr = nullptr) {
       if (golay) {
         for (int64_t k = 0; k < g; ++k) {
-          uint32_t cnt, w;
-          if (packed) {
-            const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * KVECC_GOLAY_PACKED_ROW(g) + 3 * k;
-            w = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
-          } else {
-            w = (uint32_t)reinterpret_cast<const int32_t *>(cache)[srow * g + k];
-          }
-          const uint32_t dw = golay_decode1(w, tab, tab + 4096, cnt);
+          uint32_t cnt;
+          const uint32_t dw = golay_decode1(golay_word(cache, packed, srow, g, k), tab, tab + 4096, cnt);
           for (int64_t u = 0; u < 3 && 3 * k + u < head_dim; ++u)
             kv[3 * k + u] = ((float)(dw >> (4 * u) & 0xFu) - 8.0f) * s;
         }
@@ -1096,7 +1093,7 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
     for (int64_t bh = b0; bh < e0; ++bh) {
       const int64_t b = bh / (q_len * heads), t = bh / heads % q_len, h = bh % heads, hk = h / groups;
       // the sequence's span (null: the uniform call); a padding row reads no query and sees no key
-      const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_len;
+      const auto [first, count] = span_of(q_spans, b, q_len);
       const bool valid = first >= 0 && t >= first && t < std::min(first + count, q_len);
       if (valid)
         for (int64_t j = 0; j < head_dim; ++j) q[j] = load_x(query, q_dtype, b * q_sb + t * q_st + h * q_sh + j);
@@ -1110,17 +1107,14 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
       const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
       auto slot_of = [&](int64_t pos) {  // -1: no block
         const int32_t blk = block_table[b * max_blocks + pos / block_size];
-        return blk < 0 ? (int64_t)-1
-                       : (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
+        return blk < 0 ? (int64_t)-1 : cache_slot(blk, num_layers, layer, kv_heads, hk, block_size, pos);
       };
       auto codewords = [&](const void *cache, int64_t slot) {
         return slot < 0 ? zero_row.data() : reinterpret_cast<const uint8_t *>(cache) + slot * head_dim;
       };
       for (int64_t pos = 0; pos < ctx; ++pos) {
-        const int32_t blk = block_table[b * max_blocks + pos / block_size];
-        if (blk < 0) continue;
-        const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size +
-                             pos % block_size;
+        const int64_t srow = slot_of(pos);
+        if (srow < 0) continue;
         const int64_t sl = interp ? slot_of(pos > 0 ? pos - 1 : 0) : -1;
         const int64_t sr = interp ? slot_of(pos + 1 < nb ? pos + 1 : nb - 1) : -1;
         if (interp)
@@ -1147,8 +1141,122 @@ static int cpu_attention_impl(const void *query, int64_t q_sb, int64_t q_st, int
         store_y(out, q_dtype, bh * head_dim + j, l > 0.0f ? acc[j] / l : golay ? 0.0f : -8.0f);
     }
   });
+}
+
+// The one path of the seven kvecc_cpu_paged_attention* entries, as attention.hip's
+// entries share theirs: the record of the call (workspace and stream unused: null),
+// the mode, and the thread count.
+//
+// Counting modes (m.stats a plain host buffer), after the rows -- so a repairing
+// call's output is that of the cache as it stood -- over for_each_counted_row:
+//   counted        stats[0] / stats[1] += the SINGLE_CORRECTED / DOUBLE_DETECTED bytes (h84_decode4)
+//   repair         the same counts through h84_scrub4, every word with a correctable
+//                  non-canonical byte stored back, stats[2] += bytes rewritten
+//   golay_counted  stats[0] += the decoder's counts 0..3 (bits corrected), stats[1] += the
+//                  words of count 4; bits 24-31 of an int32 word and a packed row's pad
+//                  bytes take no part (golay_decode1)
+//
+// The checks come in the order, and under the names, they have always come in.  What
+// is odd about that is kept: the messages of the shared part say cpu_paged_attention
+// whichever entry was called (and a codec that cannot interpolate cpu_paged_attention_interp),
+// the entries' own say `who`; the decode entry checks no q_len and no strides, only the
+// chunk entry calls q_len by that name, only the ragged entry needs its spans; a counting
+// call reports null stats, then its codec, before anything else; the interpolating call
+// refuses a head_dim that is no multiple of 4 ahead of the negative-size and codec checks
+// (a Hamming(8,4) counting call ahead of negative size), the others accept it for hamming84
+// (int4 and hamming74 are refused, as the device entries refuse them); `negative size` does
+// not look at q_len; a call with no rows returns before the later checks; num_blocks is not checked.
+int cpu_attention(const char *who, const AttnCall &c, const AttnMode &m, int threads) {
+  const bool decode = !std::strcmp(who, "cpu_paged_attention");
+  const bool chunk = !std::strcmp(who, "cpu_paged_attention_chunk");
+  const bool ragged = !std::strcmp(who, "cpu_paged_attention_chunk_ragged");
+  const bool counts = m.kind != AttnKind::plain, golay_counts = m.kind == AttnKind::golay_counted;
+  const bool repair = m.kind == AttnKind::repair;
+  if (counts && !m.stats) return set_error(KVECC_EINVAL, "%s: null stats", who);
+  if (golay_counts && c.codec != KVECC_CODEC_GOLAY && c.codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL, "%s: codec %d (this counted twin needs golay or golay_packed)", who, c.codec);
+  if (counts && !golay_counts && c.codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "%s: codec %d (the %s twin needs hamming84)", who, c.codec,
+                     repair ? "repairing" : "counted");
+  if (!decode) {
+    if (c.q_len < 0) return set_error(KVECC_EINVAL, "%s: negative %s", who, chunk ? "q_len" : "q_max");
+    if (ragged && !c.q_spans) return set_error(KVECC_EINVAL, "%s: null q_spans", who);
+    if (c.q_sb < 0 || c.q_st < 0 || c.q_sh < 0 || (c.heads > 1 && c.q_sh < c.head_dim) ||
+        (c.q_len > 1 && c.q_st < c.head_dim))
+      return set_error(KVECC_EINVAL, "%s: bad query strides", who);
+    if ((m.interp || (counts && !golay_counts)) && c.head_dim % 4 != 0)
+      return set_error(KVECC_EINVAL, "%s: hamming84 head_dim must be a multiple of 4", who);
+  }
+  if (c.batch < 0 || c.heads < 0 || c.kv_heads < 0 || c.head_dim < 0)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: negative size");
+  if (m.interp && c.codec != KVECC_CODEC_H84)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: codec %d (interpolation needs hamming84)", c.codec);
+  if (c.batch == 0 || c.heads == 0 || c.q_len == 0) return KVECC_OK;
+  if (c.kv_heads < 1 || c.heads % c.kv_heads != 0)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: heads not a multiple of kv heads");
+  if (c.head_dim < 1) return set_error(KVECC_EINVAL, "cpu_paged_attention: empty head_dim");
+  if (c.codec != KVECC_CODEC_NONE && c.codec != KVECC_CODEC_H74 && c.codec != KVECC_CODEC_H84 &&
+      c.codec != KVECC_CODEC_GOLAY && c.codec != KVECC_CODEC_GOLAY_PACKED)
+    return set_error(KVECC_EINVAL,
+                     "cpu_paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed only)",
+                     c.codec);
+  if ((c.codec == KVECC_CODEC_NONE || c.codec == KVECC_CODEC_H74) && c.head_dim % 4 != 0)  // as the device entries
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: %s head_dim must be a multiple of 4",
+                     c.codec == KVECC_CODEC_NONE ? "int4" : "hamming74");
+  if (c.q_dtype < KVECC_F32 || c.q_dtype > KVECC_BF16)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: bad dtype %d", c.q_dtype);
+  if (c.num_layers < 1 || c.layer < 0 || c.layer >= c.num_layers || c.block_size < 1 || c.max_blocks < 1)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: bad cache geometry");
+  if (!c.query || !c.k_cache || !c.v_cache || !c.block_table || !c.context_lens || !c.k_scales || !c.v_scales || !c.out)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention: null pointer");
+  if (m.interp)
+    attention_rows<true>(c, threads);
+  else
+    attention_rows<false>(c, threads);
+  if (!counts) return KVECC_OK;
+  uint64_t n[3] = {0, 0, 0};
+  if (golay_counts) {
+    const uint16_t *tab = host_golay_tables();
+    const bool packed = c.codec == KVECC_CODEC_GOLAY_PACKED;
+    const int64_t g = (c.head_dim + 2) / 3;
+    for_each_counted_row(c, [&](const void *cache, int64_t row) {
+      for (int64_t k = 0; k < g; ++k) {
+        uint32_t cnt;
+        golay_decode1(golay_word(cache, packed, row, g, k), tab, tab + 4096, cnt);
+        n[0] += cnt & 3u;
+        n[1] += cnt >> 2;
+      }
+    });
+  } else {
+    for_each_counted_row(c, [&](const void *cache, int64_t row) {
+      // (a repairing entry's caches are its caller's to write: kvecc_cpu_paged_attention_repair)
+      uint8_t *p = const_cast<uint8_t *>(reinterpret_cast<const uint8_t *>(cache)) + row * c.head_dim;
+      uint32_t n1 = 0, n2 = 0, nr = 0;  // of one row, summed into n
+      for (int64_t j = 0; j < c.head_dim; j += 4) {
+        const uint32_t w = load4(p + j);
+        if (repair) {
+          const uint32_t x = h84_scrub4(w, n1, n2, nr);
+          if (x) store4(p + j, w ^ x);
+        } else {
+          uint32_t d, t;
+          h84_decode4(w, d, t, n1, n2);
+        }
+      }
+      n[0] += n1;
+      n[1] += n2;
+      n[2] += nr;
+    });
+  }
+  m.stats[0] += n[0];
+  m.stats[1] += n[1];
+  if (repair) m.stats[2] += n[2];
   return KVECC_OK;
 }
+
+}  // namespace
+}  // namespace kvecc
+
+extern "C" {
 
 KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const void *k_cache,
                                         const void *v_cache, const int32_t *block_table,
@@ -1158,14 +1266,14 @@ KVECC_API int kvecc_cpu_paged_attention(const void *query, int q_dtype, const vo
                                         int64_t num_blocks, int64_t num_layers, int64_t layer, int64_t block_size,
                                         int64_t max_blocks, int64_t max_context_len,
                                         float sm_scale, int codec, int threads) {
-  return cpu_attention_impl(query, heads * head_dim, 0, head_dim, q_dtype, k_cache, v_cache, block_table,
-                            context_lens, k_scales, v_scales, out, batch, 1, heads, kv_heads, head_dim,
-                            num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale,
-                            codec, threads);
+  return cpu_attention("cpu_paged_attention",
+                       {query, heads * head_dim, 0, head_dim, q_dtype, k_cache, v_cache, block_table, context_lens,
+                        nullptr, k_scales, v_scales, out, batch, 1, heads, kv_heads, head_dim, num_blocks, num_layers,
+                        layer, block_size, max_blocks, max_context_len, sm_scale, codec, nullptr, 0, nullptr},
+                       {}, threads);
 }
 
-// Chunked causal twin (kvecc_paged_attention_chunk): the same decode and fp32
-// online softmax per (b, t, h) row, out [batch, q_len, heads, head_dim].
+// Chunked causal twin (kvecc_paged_attention_chunk): out [batch, q_len, heads, head_dim]
 KVECC_API int kvecc_cpu_paged_attention_chunk(const void *query, int64_t q_batch_stride,
                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                               const void *k_cache, const void *v_cache,
@@ -1175,14 +1283,12 @@ KVECC_API int kvecc_cpu_paged_attention_chunk(const void *query, int64_t q_batch
                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
                                               int64_t layer, int64_t block_size, int64_t max_blocks,
                                               int64_t max_context_len, float sm_scale, int codec, int threads) {
-  if (q_len < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk: negative q_len");
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_len > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk: bad query strides");
-  return cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                            block_table, context_lens, k_scales, v_scales, out, batch, q_len, heads, kv_heads,
-                            head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
-                            sm_scale, codec, threads);
+  return cpu_attention("cpu_paged_attention_chunk",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, nullptr, k_scales, v_scales, out, batch, q_len, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       {}, threads);
 }
 
 // Ragged twin (kvecc_paged_attention_chunk_ragged): per-sequence query spans, padding rows the empty value
@@ -1197,20 +1303,15 @@ KVECC_API int kvecc_cpu_paged_attention_chunk_ragged(const void *query, int64_t 
                                                      int64_t layer, int64_t block_size, int64_t max_blocks,
                                                      int64_t max_context_len, float sm_scale, int codec,
                                                      int threads) {
-  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk_ragged: negative q_max");
-  if (!q_spans) return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk_ragged: null q_spans");
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_chunk_ragged: bad query strides");
-  return cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                            block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads, kv_heads,
-                            head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
-                            sm_scale, codec, threads, q_spans);
+  return cpu_attention("cpu_paged_attention_chunk_ragged",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       {}, threads);
 }
 
-// Interpolating twin (kvecc_paged_attention_interp): every stored byte through h84_decode4,
-// doubles through interp_word of the neighbouring tokens (clamped to the sequence), then the
-// attention above; q_spans may be null
+// Interpolating twin (kvecc_paged_attention_interp); q_spans may be null
 KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batch_stride,
                                                int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                                const void *k_cache, const void *v_cache,
@@ -1222,86 +1323,16 @@ KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batc
                                                int64_t layer, int64_t block_size, int64_t max_blocks,
                                                int64_t max_context_len, float sm_scale, int codec,
                                                int threads) {
-  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: negative q_max");
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: bad query strides");
-  if (head_dim % 4 != 0)
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_interp: hamming84 head_dim must be a multiple of 4");
-  return cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                            block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads, kv_heads,
-                            head_dim, num_blocks, num_layers, layer, block_size, max_blocks, max_context_len,
-                            sm_scale, codec, threads, q_spans, true);
+  return cpu_attention("cpu_paged_attention_interp",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       {AttnKind::plain, true}, threads);
 }
 
 // Counted twin (kvecc_paged_attention_stats): the ragged (interp == 0) or the interpolating
-// twin's output, and the SINGLE_CORRECTED / DOUBLE_DETECTED classification of every stored K and
-// V byte of the first n_b positions of each sequence that has a valid query token -- once per
-// (sequence, cache head), whatever the query rows and heads that look at it.  stats is a host
-// buffer: the totals go to stats[0] / stats[1].
-// Repairing twin (kvecc_paged_attention_repair, `repair`): the same output -- computed first, on
-// the cache as it stood -- and the same counts, and h84_scrub4 over the same region: every counted
-// word with a correctable non-canonical byte is stored back, stats[2] += bytes rewritten.
-static int cpu_attention_stats_impl(const char *who, bool repair, const void *query, int64_t q_batch_stride,
-                                    int64_t q_token_stride, int64_t q_head_stride, int q_dtype, void *k_cache,
-                                    void *v_cache, const int32_t *block_table, const int32_t *context_lens,
-                                    const int32_t *q_spans, const float *k_scales, const float *v_scales,
-                                    void *out, int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
-                                    int64_t head_dim, int64_t num_blocks, int64_t num_layers, int64_t layer,
-                                    int64_t block_size, int64_t max_blocks, int64_t max_context_len,
-                                    float sm_scale, int codec, int interp, uint64_t *stats, int threads) {
-  if (!stats) return set_error(KVECC_EINVAL, "%s: null stats", who);
-  if (codec != KVECC_CODEC_H84)
-    return set_error(KVECC_EINVAL, "%s: codec %d (the %s twin needs hamming84)", who, codec,
-                     repair ? "repairing" : "counted");
-  if (q_max < 0) return set_error(KVECC_EINVAL, "%s: negative q_max", who);
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "%s: bad query strides", who);
-  if (head_dim % 4 != 0) return set_error(KVECC_EINVAL, "%s: hamming84 head_dim must be a multiple of 4", who);
-  const int rc = cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, threads, q_spans, interp != 0);
-  if (rc != KVECC_OK || batch == 0 || heads == 0 || q_max == 0) return rc;
-  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
-  uint32_t n1 = 0, n2 = 0, nr = 0;
-  uint64_t c1 = 0, c2 = 0, cr = 0;
-  for (int64_t b = 0; b < batch; ++b) {
-    const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_max;
-    if (first < 0 || count <= 0 || first >= q_max) continue;  // all padding: the sequence is not read
-    const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
-    for (int64_t pos = 0; pos < nb; ++pos) {
-      const int32_t blk = block_table[b * max_blocks + pos / block_size];
-      if (blk < 0) continue;
-      for (int64_t hk = 0; hk < kv_heads; ++hk) {
-        const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
-        for (void *cache : {k_cache, v_cache}) {
-          uint8_t *c = reinterpret_cast<uint8_t *>(cache) + srow * head_dim;
-          for (int64_t j = 0; j < head_dim; j += 4) {
-            const uint32_t w = load4(c + j);
-            if (repair) {
-              const uint32_t x = h84_scrub4(w, n1, n2, nr);
-              if (x) store4(c + j, w ^ x);
-            } else {
-              uint32_t d, t;
-              h84_decode4(w, d, t, n1, n2);
-            }
-          }
-        }
-        c1 += n1;
-        c2 += n2;
-        cr += nr;
-        n1 = n2 = nr = 0;
-      }
-    }
-  }
-  stats[0] += c1;
-  stats[1] += c2;
-  if (repair) stats[2] += cr;
-  return KVECC_OK;
-}
-
+// twin's output and the Hamming(8,4) counts; stats is a host buffer
 KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch_stride,
                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                               const void *k_cache, const void *v_cache,
@@ -1313,14 +1344,16 @@ KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch
                                               int64_t layer, int64_t block_size, int64_t max_blocks,
                                               int64_t max_context_len, float sm_scale, int codec, int interp,
                                               uint64_t *stats, int threads) {
-  // (the caches are only read: `repair` false)
-  return cpu_attention_stats_impl("cpu_paged_attention_stats", false, query, q_batch_stride, q_token_stride,
-                                  q_head_stride, q_dtype, const_cast<void *>(k_cache), const_cast<void *>(v_cache),
-                                  block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
-                                  kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                  max_context_len, sm_scale, codec, interp, stats, threads);
+  return cpu_attention("cpu_paged_attention_stats",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       {AttnKind::counted, interp != 0, stats}, threads);
 }
 
+// Repairing twin (kvecc_paged_attention_repair): the counted twin's output and counts, the
+// counted region of k_cache / v_cache rewritten in place
 KVECC_API int kvecc_cpu_paged_attention_repair(const void *query, int64_t q_batch_stride,
                                                int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                                void *k_cache, void *v_cache, const int32_t *block_table,
@@ -1331,18 +1364,16 @@ KVECC_API int kvecc_cpu_paged_attention_repair(const void *query, int64_t q_batc
                                                int64_t layer, int64_t block_size, int64_t max_blocks,
                                                int64_t max_context_len, float sm_scale, int codec, int interp,
                                                uint64_t *stats, int threads) {
-  return cpu_attention_stats_impl("cpu_paged_attention_repair", true, query, q_batch_stride, q_token_stride,
-                                  q_head_stride, q_dtype, k_cache, v_cache, block_table, context_lens, q_spans,
-                                  k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim, num_blocks,
-                                  num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
-                                  interp, stats, threads);
+  return cpu_attention("cpu_paged_attention_repair",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       {AttnKind::repair, interp != 0, stats}, threads);
 }
 
-// Golay counted twin (kvecc_paged_attention_golay_stats): the ragged twin's output (q_spans may be
-// null), and the decoder's count of each of the g codewords of every K and V row of the first n_b
-// positions of each sequence that has a valid query token -- once per (sequence, cache head):
-// stats[0] += the counts 0..3 (bits corrected), stats[1] += the words of count 4 (uncorrectable).
-// Bits 24-31 of an int32 word and a packed row's pad bytes take no part (golay_decode1).
+// Golay counted twin (kvecc_paged_attention_golay_stats): the ragged twin's output (q_spans may
+// be null) and the Golay decoder's counts
 KVECC_API int kvecc_cpu_paged_attention_golay_stats(const void *query, int64_t q_batch_stride,
                                                     int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
                                                     const void *k_cache, const void *v_cache,
@@ -1354,59 +1385,12 @@ KVECC_API int kvecc_cpu_paged_attention_golay_stats(const void *query, int64_t q
                                                     int64_t layer, int64_t block_size, int64_t max_blocks,
                                                     int64_t max_context_len, float sm_scale, int codec,
                                                     uint64_t *stats, int threads) {
-  if (!stats) return set_error(KVECC_EINVAL, "cpu_paged_attention_golay_stats: null stats");
-  if (codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL,
-                     "cpu_paged_attention_golay_stats: codec %d (this counted twin needs golay or golay_packed)", codec);
-  if (q_max < 0) return set_error(KVECC_EINVAL, "cpu_paged_attention_golay_stats: negative q_max");
-  if (q_batch_stride < 0 || q_token_stride < 0 || q_head_stride < 0 ||
-      (heads > 1 && q_head_stride < head_dim) || (q_max > 1 && q_token_stride < head_dim))
-    return set_error(KVECC_EINVAL, "cpu_paged_attention_golay_stats: bad query strides");
-  const int rc = cpu_attention_impl(query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
-                                    block_table, context_lens, k_scales, v_scales, out, batch, q_max, heads,
-                                    kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
-                                    max_context_len, sm_scale, codec, threads, q_spans);
-  if (rc != KVECC_OK || batch == 0 || heads == 0 || q_max == 0) return rc;
-  if (max_context_len <= 0) max_context_len = max_blocks * block_size;
-  static uint16_t tab[8192];
-  static bool ready = [] {
-    build_golay_parity_table(tab);
-    build_golay_correct_table(tab + 4096);
-    return true;
-  }();
-  (void)ready;
-  const bool packed = codec == KVECC_CODEC_GOLAY_PACKED;
-  const int64_t g = (head_dim + 2) / 3;
-  uint64_t bits = 0, unc = 0;
-  for (int64_t b = 0; b < batch; ++b) {
-    const int64_t first = q_spans ? q_spans[3 * b] : 0, count = q_spans ? q_spans[3 * b + 1] : q_max;
-    if (first < 0 || count <= 0 || first >= q_max) continue;  // all padding: the sequence is not read
-    const int64_t nb = std::min<int64_t>(std::min<int64_t>(context_lens[b], max_context_len), max_blocks * block_size);
-    for (int64_t pos = 0; pos < nb; ++pos) {
-      const int32_t blk = block_table[b * max_blocks + pos / block_size];
-      if (blk < 0) continue;
-      for (int64_t hk = 0; hk < kv_heads; ++hk) {
-        const int64_t srow = (((int64_t)blk * num_layers + layer) * kv_heads + hk) * block_size + pos % block_size;
-        for (const void *cache : {k_cache, v_cache}) {
-          for (int64_t k = 0; k < g; ++k) {
-            uint32_t cnt, w;
-            if (packed) {
-              const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * KVECC_GOLAY_PACKED_ROW(g) + 3 * k;
-              w = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
-            } else {
-              w = (uint32_t)reinterpret_cast<const int32_t *>(cache)[srow * g + k];
-            }
-            golay_decode1(w, tab, tab + 4096, cnt);
-            bits += cnt & 3u;
-            unc += cnt >> 2;
-          }
-        }
-      }
-    }
-  }
-  stats[0] += bits;
-  stats[1] += unc;
-  return KVECC_OK;
+  return cpu_attention("cpu_paged_attention_golay_stats",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       {AttnKind::golay_counted, false, stats}, threads);
 }
 
 }  // extern "C"

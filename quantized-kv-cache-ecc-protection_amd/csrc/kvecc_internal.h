@@ -107,6 +107,47 @@ inline unsigned grid_for(int64_t work, int64_t per_block, int per_cu = 8) {
 
 inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// ---- the paged-attention entries' call record (attention.hip, cpu.hip) ---------
+// A call's parameters, in the order and under the names of kvecc.h's chunk-family
+// entries (the decode entry: q_len 1, no spans, its strides unused).  The host
+// twin leaves workspace, workspace_floats and stream null: it takes a thread
+// count next to the record.
+struct AttnCall {
+  const void *query;
+  int64_t q_sb, q_st, q_sh;
+  int q_dtype;
+  const void *k_cache, *v_cache;
+  const int32_t *block_table, *context_lens, *q_spans;
+  const float *k_scales, *v_scales;
+  void *out;
+  int64_t batch, q_len, heads, kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks;
+  int64_t max_context_len;
+  float sm_scale;
+  int codec;
+  float *workspace;
+  int64_t workspace_floats;
+  void *stream;
+};
+
+// Which chunk-family entry a call came through.  q_spans (AttnCall) is null for
+// kvecc_paged_attention_chunk and the device spans for the ragged entry (q_len its
+// q_max); nothing but the kernels reads the spans: the launch geometry is the
+// uniform call's.
+enum class AttnKind {
+  plain,          // kvecc_paged_attention_chunk / _chunk_ragged / _interp
+  counted,        // kvecc_paged_attention_stats: Hamming(8,4), stats[0..1]
+  golay_counted,  // kvecc_paged_attention_golay_stats: golay / golay_packed, no interpolation
+  repair,         // kvecc_paged_attention_repair: the counted call's geometry and argument values
+                  // over the repairing kernels, stats[2] too
+};
+struct AttnMode {
+  AttnKind kind = AttnKind::plain;
+  // Hamming(8,4) caches under 4 GiB through the interpolating kernels at every q_len (q_len 1
+  // included: the decode entry's kernels do not interpolate)
+  bool interp = false;
+  uint64_t *stats = nullptr;  // every kind but plain: the library's sharded statistics buffer (the twin: a host array)
+};
+
 // ---- device helpers ----------------------------------------------------------
 
 // Phase boundary of a wave-private LDS tile (lanes exchange data through LDS

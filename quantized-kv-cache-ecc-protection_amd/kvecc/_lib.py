@@ -67,27 +67,7 @@ SIGNATURES = {
     "kvecc_shim_read_batch": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int,
                               _vp, _vp, _int, _vp, _vp],
     "kvecc_paged_attention_workspace": [_i64, _i64, _i64, _i64],
-    "kvecc_paged_attention": [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
-                              _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp, _i64, _vp],
     "kvecc_paged_attention_chunk_workspace": [_i64, _i64, _i64, _i64, _i64],
-    "kvecc_paged_attention_chunk": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
-                                    _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _vp, _i64,
-                                    _vp],
-    "kvecc_paged_attention_chunk_ragged": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                           _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
-                                           _vp, _i64, _vp],
-    "kvecc_paged_attention_interp": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                     _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
-                                     _vp, _i64, _vp],
-    "kvecc_paged_attention_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                    _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int,
-                                    _vp, _vp, _i64, _vp],
-    "kvecc_paged_attention_repair": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                     _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int,
-                                     _vp, _vp, _i64, _vp],
-    "kvecc_paged_attention_golay_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                          _f32, _int, _vp, _vp, _i64, _vp],
     "kvecc_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                           _int, _vp, _vp],
     "kvecc_cpu_cache_scrub": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -121,27 +101,33 @@ SIGNATURES = {
     "kvecc_cpu_shim_read": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _int, _vp, _int],
     "kvecc_cpu_shim_read_batch": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int,
                                   _int, _vp, _vp, _int, _vp, _int],
-    "kvecc_cpu_paged_attention": [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                                  _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int, _int],
-    "kvecc_cpu_paged_attention_chunk": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _int,
-                                        _int],
-    "kvecc_cpu_paged_attention_chunk_ragged": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                               _f32, _int, _int],
-    "kvecc_cpu_paged_attention_interp": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                         _f32, _int, _int],
-    "kvecc_cpu_paged_attention_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                        _f32, _int, _int, _vp, _int],
-    "kvecc_cpu_paged_attention_repair": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                         _f32, _int, _int, _vp, _int],
-    "kvecc_cpu_paged_attention_golay_stats": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                              _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                              _i64, _f32, _int, _vp, _int],
 }
+
+
+# The paged-attention entries (include/kvecc.h), on both backends: the decode entry
+# and the chunk family, whose entries add to kvecc_paged_attention_chunk's list
+# (q_spans, the interp flag, stats).  The device entries end with (workspace,
+# workspace_floats, stream), the host twins with their thread count.
+_CHUNK_ENTRY_EXTRAS = {"chunk": (False, False, False), "chunk_ragged": (True, False, False),
+                       "interp": (True, False, False), "stats": (True, True, True),
+                       "repair": (True, True, True), "golay_stats": (True, False, True)}
+
+
+def _attention_signatures():
+    sigs = {}
+    for prefix, tail in (("kvecc_", [_vp, _i64, _vp]), ("kvecc_cpu_", [_int])):
+        # query, q_dtype | caches, table, lengths, scales, out | batch .. max_context_len | sm_scale, codec
+        sigs[prefix + "paged_attention"] = [_vp, _int] + [_vp] * 7 + [_i64] * 10 + [_f32, _int] + tail
+        for entry, (spans, interp, stats) in _CHUNK_ENTRY_EXTRAS.items():
+            sigs[f"{prefix}paged_attention_{entry}"] = (
+                [_vp, _i64, _i64, _i64, _int]  # query, its three strides, q_dtype
+                + [_vp] * 4 + [_vp] * spans + [_vp] * 3  # caches, table, lengths | q_spans | scales, out
+                + [_i64] * 11 + [_f32, _int]  # batch, q_len .. max_context_len | sm_scale, codec
+                + [_int] * interp + [_vp] * stats + tail)
+    return sigs
+
+
+SIGNATURES.update(_attention_signatures())
 _RESTYPE = {
     "kvecc_version": ctypes.c_char_p,
     "kvecc_last_error": ctypes.c_char_p,

@@ -25,6 +25,7 @@ import threading
 import torch
 
 from . import _lib
+from ._lib import _CHUNK_ENTRY_EXTRAS  # what a chunk-family entry adds to the shared argument list
 from .config import ErrorType
 
 _VP = ctypes.c_void_p
@@ -1097,16 +1098,19 @@ def _attn_workspace(device, n):
     return ws
 
 
-def _check_attention_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                          out, block_size, codec):
+# The argument checks of the attention entries, in ordered pieces: the decode
+# entry's (_check_attention_args) and the chunk family's (_check_attention_rest,
+# between the checks of its own query and out) run them in the same sequence.
+def _check_attn_codec(codec):
     if codec not in _ATTN_CACHE_DT:
         raise ValueError(f"paged attention codec {codec!r} ({_ATTN_CODEC_NAMES})")
-    if query.dim() != 3 or query.dtype not in _DT:
-        raise ValueError(f"query must be [B, H, D] fp32/fp16/bf16, got {tuple(query.shape)} {query.dtype}")
-    batch, heads, head_dim = query.shape
+
+
+def _check_attn_caches(heads, head_dim, k_cache, v_cache, block_size, codec):
+    """Cache dtypes and geometry against the codec and block_size."""
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
         raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
-    nb, nl, kvh, row = k_cache.shape
+    kvh, row = k_cache.shape[2:]
     per = _ATTN_ROW_WORDS[codec](head_dim)
     for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
         if c.dtype != _ATTN_CACHE_DT[codec]:
@@ -1116,6 +1120,11 @@ def _check_attention_args(query, k_cache, v_cache, block_table, context_lens, k_
                          f"{block_size * per}")
     if kvh < 1 or heads % kvh:
         raise ValueError(f"{heads} query heads not a multiple of {kvh} kv heads")
+
+
+def _check_attn_tables(batch, k_cache, block_table, context_lens, k_scales, v_scales, block_size):
+    """Table and lengths against the batch, scales against the caches."""
+    nb, nl, kvh, _ = k_cache.shape
     if block_table.dim() != 2 or block_table.shape[0] != batch or block_table.dtype != torch.int32:
         raise ValueError("block_table must be int32 [B, max_blocks]")
     if context_lens.shape != (batch,) or context_lens.dtype != torch.int32:
@@ -1124,51 +1133,40 @@ def _check_attention_args(query, k_cache, v_cache, block_table, context_lens, k_
         if sc.shape != (nb, nl, kvh, block_size) or sc.dtype != torch.float32:
             raise ValueError(f"{name} must be float32 [{nb}, {nl}, {kvh}, {block_size}], got "
                              f"{tuple(sc.shape)} {sc.dtype}")
-    if out.shape != query.shape or out.dtype not in _DT:
-        raise ValueError("out must match query's [B, H, D]")
-    for name, t in (("query", query), ("k_cache", k_cache), ("v_cache", v_cache),
-                    ("block_table", block_table), ("context_lens", context_lens),
-                    ("k_scales", k_scales), ("v_scales", v_scales), ("out", out)):
-        if t.device != query.device:
-            raise ValueError(f"{name} is on {t.device}, query on {query.device}")
+
+
+def _check_attn_placement(device, **tensors):
+    """One device (the query's) and contiguity, in the order given."""
+    for name, t in tensors.items():
+        if t.device != device:
+            raise ValueError(f"{name} is on {t.device}, query on {device}")
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
+
+
+def _check_attention_args(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                          out, block_size, codec):
+    _check_attn_codec(codec)
+    if query.dim() != 3 or query.dtype not in _DT:
+        raise ValueError(f"query must be [B, H, D] fp32/fp16/bf16, got {tuple(query.shape)} {query.dtype}")
+    batch, heads, head_dim = query.shape
+    _check_attn_caches(heads, head_dim, k_cache, v_cache, block_size, codec)
+    _check_attn_tables(batch, k_cache, block_table, context_lens, k_scales, v_scales, block_size)
+    if out.shape != query.shape or out.dtype not in _DT:
+        raise ValueError("out must match query's [B, H, D]")
+    _check_attn_placement(query.device, query=query, k_cache=k_cache, v_cache=v_cache, block_table=block_table,
+                          context_lens=context_lens, k_scales=k_scales, v_scales=v_scales, out=out)
 
 
 def _check_attention_rest(batch, heads, head_dim, device, k_cache, v_cache, block_table, context_lens,
                           k_scales, v_scales, block_size, codec):
     """The chunked entry's checks of everything but the query and out, as
-    _check_attention_args makes them for the decode entry: cache dtypes and
-    geometry against the codec and block_size, table and lengths against the
-    batch, one device, contiguity."""
-    if codec not in _ATTN_CACHE_DT:
-        raise ValueError(f"paged attention codec {codec!r} ({_ATTN_CODEC_NAMES})")
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
-        raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
-    nb, nl, kvh, row = k_cache.shape
-    per = _ATTN_ROW_WORDS[codec](head_dim)
-    for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if c.dtype != _ATTN_CACHE_DT[codec]:
-            raise ValueError(f"{codec} {name} must be {_ATTN_CACHE_DT[codec]}, got {c.dtype}")
-    if row != block_size * per:
-        raise ValueError(f"{codec} cache rows hold {row} words, expected block_size*{per} = "
-                         f"{block_size * per}")
-    if kvh < 1 or heads % kvh:
-        raise ValueError(f"{heads} query heads not a multiple of {kvh} kv heads")
-    if block_table.dim() != 2 or block_table.shape[0] != batch or block_table.dtype != torch.int32:
-        raise ValueError("block_table must be int32 [B, max_blocks]")
-    if context_lens.shape != (batch,) or context_lens.dtype != torch.int32:
-        raise ValueError("context_lens must be int32 [B]")
-    for name, sc in (("k_scales", k_scales), ("v_scales", v_scales)):
-        if sc.shape != (nb, nl, kvh, block_size) or sc.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32 [{nb}, {nl}, {kvh}, {block_size}], got "
-                             f"{tuple(sc.shape)} {sc.dtype}")
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache), ("block_table", block_table),
-                    ("context_lens", context_lens), ("k_scales", k_scales), ("v_scales", v_scales)):
-        if t.device != device:
-            raise ValueError(f"{name} is on {t.device}, query on {device}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
+    _check_attention_args makes them for the decode entry."""
+    _check_attn_codec(codec)
+    _check_attn_caches(heads, head_dim, k_cache, v_cache, block_size, codec)
+    _check_attn_tables(batch, k_cache, block_table, context_lens, k_scales, v_scales, block_size)
+    _check_attn_placement(device, k_cache=k_cache, v_cache=v_cache, block_table=block_table,
+                          context_lens=context_lens, k_scales=k_scales, v_scales=v_scales)
 
 
 def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
@@ -1236,15 +1234,6 @@ def _check_interp_codec(codec):
 def _check_stats_codec(codec):
     if codec != "hamming84":
         raise ValueError(f"stats needs hamming84 (the counted attention kernels), got codec {codec!r}")
-
-
-# The chunk-family entries (kvecc_paged_attention_<entry>, and the host twins
-# kvecc_cpu_paged_attention_<entry>) share one argument list; these are the
-# arguments an entry adds to kvecc_paged_attention_chunk's: (q_spans, the interp
-# flag, stats)
-_CHUNK_ENTRY_EXTRAS = {"chunk": (False, False, False), "chunk_ragged": (True, False, False),
-                       "interp": (True, False, False), "stats": (True, True, True),
-                       "repair": (True, True, True), "golay_stats": (True, False, True)}
 
 
 def _chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
