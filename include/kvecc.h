@@ -564,6 +564,66 @@ KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_st
                                            int64_t max_context_len, float sm_scale, int codec,
                                            float *workspace, int64_t workspace_floats, void *stream);
 
+/* ---- Windowed attention ------------------------------------------------------ */
+/* Sliding-window paged attention with sink tokens (Mistral-style masking over the
+ * stored, post-RoPE keys: positions stay absolute, nothing in the cache is
+ * re-indexed; no reference counterpart).  The arguments up to codec, the
+ * workspace (kvecc_paged_attention_chunk_workspace at q_len = q_max), the query
+ * strides, the output layout [batch, q_max, heads, head_dim], head_dim <= 256,
+ * the GQA map, the spans and the max_context_len clamp are
+ * kvecc_paged_attention_chunk_ragged's, except that q_spans may be NULL (the
+ * uniform call: first 0, count q_max) and q_max 1 is allowed and is the decode
+ * step.  codec: KVECC_CODEC_H84, _H74, _NONE, _GOLAY or _GOLAY_PACKED; query
+ * dtypes fp32, fp16, bf16.  Plain attention only: no interpolation, no
+ * statistics, no repair.
+ *
+ * window = W >= 0 and sinks = S >= 0; a negative one is KVECC_EINVAL.  For a
+ * valid query row at position p (the ragged entry's rule) and ctx_cap =
+ * min(max_context_len, max_blocks * block_size), key j is visible iff all of
+ *   0 <= j <= p;   j < ctx_cap;   its block-table entry is >= 0;
+ *   j < S  or  j > p - W.
+ * A key that is both a sink and inside the window counts once.  A row with no
+ * visible key gets the entry's empty value (-8.0 for the byte codecs, 0 for
+ * Golay), per row; a padding row reads no query, and a workgroup whose rows are
+ * all padding reads no table and no cache.  A workgroup whose stretch of the
+ * context holds no key that any of its rows can see reads no table and no cache
+ * either.  A stored row that no row of a workgroup can see is not fetched for
+ * its own sake and takes no part in the arithmetic (a masked lane reads row 0 of
+ * the cache instead, as for a -1 block, with weight and V scale forced to 0):
+ * what lies in an invisible row -- a released block's bytes, a scale that is no
+ * number -- reaches no output.
+ *
+ * W == 0 means no window: the call is kvecc_paged_attention_chunk_ragged's (or,
+ * with NULL spans, kvecc_paged_attention_chunk's) and returns its bits; S is
+ * ignored.  So is W >= ctx_cap, a window that covers every key a row below
+ * ctx_cap can see -- also for a sequence whose context_lens exceeds ctx_cap
+ * (its rows sit past the keys that are attended at all), where this sentence
+ * takes precedence over the rule above.  Otherwise the kernels (matrix-core
+ * tiles or the general path, heads per workgroup) are chosen as the ragged entry
+ * chooses them, and the grid follows the window, not the context: ceil(S /
+ * split) splits sit at the start of the context, and each workgroup places the
+ * remaining ones at its own window, which it finds from context_lens -- the
+ * caller promises nothing about the lengths.  Their number spans W + split - 1
+ * keys (and the 15 later positions of a 16-column tile), at the split size the
+ * launcher would pick for a context of S + W keys, doubled until the partials
+ * fit the size kvecc_paged_attention_chunk_workspace returns for the call (the
+ * plan never looks at workspace_floats beyond the check against that size, so a
+ * larger buffer changes no bit); so grid, workspace traffic and combine width scale with
+ * S + W + q_max.  Where that is no fewer splits than the whole context's, the
+ * ragged entry's geometry is used as it is.  Results do not depend on the plan
+ * beyond fp32 summation order. */
+KVECC_API int kvecc_paged_attention_window(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                           int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                           const void *v_cache, const int32_t *block_table,
+                                           const int32_t *context_lens, const int32_t *q_spans,
+                                           const float *k_scales, const float *v_scales, void *out,
+                                           int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                           int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                           int64_t layer, int64_t block_size, int64_t max_blocks,
+                                           int64_t max_context_len, float sm_scale, int codec, int64_t window,
+                                           int64_t sinks, float *workspace, int64_t workspace_floats,
+                                           void *stream);
+
 /* ---- Counted attention ------------------------------------------------------- */
 /* Paged attention over a Hamming(8,4) cache that keeps the decode statistics of
  * the bytes it reads (no reference counterpart: the reference kernel discards
@@ -928,6 +988,19 @@ KVECC_API int kvecc_cpu_paged_attention_interp(const void *query, int64_t q_batc
                                                int64_t layer, int64_t block_size, int64_t max_blocks,
                                                int64_t max_context_len, float sm_scale, int codec,
                                                int threads);
+/* host twin of kvecc_paged_attention_window (q_spans may be NULL; fp32 throughout; window 0
+ * is the ragged / chunk twin's bits) */
+KVECC_API int kvecc_cpu_paged_attention_window(const void *query, int64_t q_batch_stride,
+                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                               const void *k_cache, const void *v_cache,
+                                               const int32_t *block_table, const int32_t *context_lens,
+                                               const int32_t *q_spans, const float *k_scales,
+                                               const float *v_scales, void *out, int64_t batch,
+                                               int64_t q_max, int64_t heads, int64_t kv_heads,
+                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                               int64_t layer, int64_t block_size, int64_t max_blocks,
+                                               int64_t max_context_len, float sm_scale, int codec,
+                                               int64_t window, int64_t sinks, int threads);
 /* host twin of kvecc_paged_attention_stats (q_spans may be NULL; stats a host buffer whose
  * words 0 and 1 take the totals) */
 KVECC_API int kvecc_cpu_paged_attention_stats(const void *query, int64_t q_batch_stride,

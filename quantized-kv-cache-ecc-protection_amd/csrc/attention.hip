@@ -228,13 +228,49 @@ template <typename A>
 constexpr bool is_byte = std::is_same<A, ByteAttnArgs>::value || std::is_same<A, ByteChunkArgs>::value ||
                          std::is_same<A, ByteUniformArgs>::value;
 
+// Windowed calls (kvecc_paged_attention_window, kvecc.h "Windowed attention") run
+// kernels of their own names over an argument block of their own type: every other
+// kernel keeps its block, its text and its registers.  A query row at position p
+// sees key j < its key limit iff j < sinks or j >= lo = max(p - window + 1, 0).
+// One byte family serves Hamming(8,4), Hamming(7,4) and unprotected INT4: `tab`
+// selects the decode table as ByteChunkArgs::tab does, KVECC_CODEC_H84 a third value.
+//
+// The grid follows the window, not the context.  Split index i < sink_splits covers the keys
+// [i * split, (i + 1) * split): the sink keys, and whatever else its rows see there.  The
+// later indices cover nsplit - sink_splits consecutive splits that START AT THE WORKGROUP'S OWN
+// WINDOW: at split max(lo / split, sink_splits), lo the row's (the tile's smallest) lower bound,
+// which the workgroup reads from context_lens -- the host promises nothing.  The launcher sizes
+// nsplit so that those splits reach past the row's (the tile's last) position (paged_attention_chunk_impl), so
+// grid, workspace traffic and combine width scale with sinks + window + q_max.  sink_splits ==
+// nsplit is the dense plan: split i at i * split, the whole context.
+struct WindowArgs : RaggedArgs {
+  uint32_t window, sinks;  // window >= 1; both clamped to INT32_MAX by the entry
+  uint32_t tab;            // KVECC_CODEC_H84, KVECC_CODEC_H74 or KVECC_CODEC_NONE (Golay kernels: unused)
+  uint32_t sink_splits;    // the leading split indices that sit at their own place
+  // first key of split index i of a workgroup whose lower key bound is lo
+  __device__ __forceinline__ int64_t split_start(uint32_t i, int64_t lo) const {
+    if (i < sink_splits) return (int64_t)i * split;
+    return (max<int64_t>(lo / split, sink_splits) + (i - sink_splits)) * split;
+  }
+};
+template <typename A>
+constexpr bool is_window = std::is_same<A, WindowArgs>::value;
+
 // Entry b of a workgroup's decode table, as a nibble: data(b) of kvecc.h's
 // attention contract.  Hamming(8,4): single errors corrected, doubles keep their
 // data.  The byte family: Hamming(7,4) -- bit 7 ignored, doubles miscorrected,
 // as h74_decode4 does everywhere -- or the low nibble of an unprotected byte.
 template <typename A>
 __device__ __forceinline__ uint32_t byte_table_nibble(const A &a, uint32_t b) {
-  if constexpr (is_byte<A>) {
+  if constexpr (is_window<A>) {  // the windowed family: all three byte tables
+    if (a.tab == KVECC_CODEC_NONE) return b & 0xFu;
+    uint32_t q, t, n1 = 0, n2 = 0;
+    if (a.tab == KVECC_CODEC_H74)
+      h74_decode4(b, q, t, n1);
+    else
+      h84_decode4(b, q, t, n1, n2);
+    return q & 0xFu;
+  } else if constexpr (is_byte<A>) {
     if (a.tab == KVECC_CODEC_NONE) return b & 0xFu;
     uint32_t q, f, n = 0;
     h74_decode4(b, q, f, n);
@@ -778,6 +814,18 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_byte_chunk_kernel(Byt
 #include "attn_split_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the windowed entry's kernels (kvecc_paged_attention_window): the chunk form with the [window]
+// islands, every codec and query dtype; Hamming(8,4)'s instantiations serve the byte family too
+// (WindowArgs::tab)
+template <typename T, int CODEC, int VEC, int W, bool BUF, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_window_kernel(WindowArgs a) {
+  constexpr int UR = 0, DEC = 0;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_WINDOW 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_WINDOW
+#undef ATTN_BODY_CHUNK
+}
 
 // ---- GQA on the matrix cores (Hamming(8,4), fp16 queries) -----------------------
 //
@@ -949,6 +997,30 @@ struct ChunkMapT {
   }
 };
 
+// The windowed kernels' map: the ragged map plus the column's lower key bound and the
+// tile's smallest (its first valid token's).  Column (tq, hq) at position p = first + tq - 1
+// sees key j < lim iff j < sinks or j >= lo = max(p - window + 1, 0); the workgroup stages
+// the cache rows some column of the tile can see -- [0, sinks) and [lo_min, ctx) -- and each
+// lane masks the scores below its own column's lo ([score mask]).  A type of its own, so
+// that ChunkMapT and the kernels over it keep their text.
+struct WindowMap : ChunkMapT<RaggedArgs> {
+  int64_t lo, lo_min;
+  __device__ __forceinline__ WindowMap(const WindowArgs &a, int n) : ChunkMapT<RaggedArgs>(a, n) {
+    lo = lo_min = 0;
+    if (any) {
+      const ChunkSpan sp(a, b);
+      const uint32_t tpt = 16u >> a.cg_log2;
+      const int64_t first = sp.lim0(a, b), tv0 = max<int64_t>(sp.v0(), (int64_t)tile * tpt);
+      lo_min = max<int64_t>(first + tv0 - (int64_t)a.window, 0);
+      lo = col_ok ? max<int64_t>(first + tq - (int64_t)a.window, 0) : 0;
+    }
+  }
+  // a bound relative to the split's first token t0, as an int the lanes compare token indices against
+  __device__ __forceinline__ static int rel(int64_t x, int64_t t0) {
+    return (int)max<int64_t>(min<int64_t>(x - t0, kMaxSplit + kMfmaStep), 0);
+  }
+};
+
 template <int D, int G>
 __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_kernel(AttnArgs a) {
 #define ATTN_BODY_CHUNK 0
@@ -1054,6 +1126,18 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_byte_mfma_ragged_kernel(
 #include "attn_h84_mfma_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the windowed entry's (kvecc_paged_attention_window): the ragged form with the [window] islands,
+// the decode table by WindowArgs::tab (Hamming(8,4), Hamming(7,4) or unprotected INT4)
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_window_kernel(WindowArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = WindowMap;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_WINDOW 1
+#include "attn_h84_mfma_body.inc"
+#undef ATTN_BODY_WINDOW
+#undef ATTN_BODY_CHUNK
+}
 
 // ---- GQA on the matrix cores, Golay(24,12) int32 caches, head_dim 128 ---------
 //
@@ -1107,6 +1191,17 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_stats_kernel(
 #define ATTN_BODY_STATS 1
 #include "attn_golay_mfma_body.inc"
 #undef ATTN_BODY_STATS
+#undef ATTN_BODY_CHUNK
+}
+// the windowed entry's (kvecc_paged_attention_window): the ragged form with the [window] islands
+template <bool PACKED>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_golay_mfma_window_kernel(WindowArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = WindowMap;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_WINDOW 1
+#include "attn_golay_mfma_body.inc"
+#undef ATTN_BODY_WINDOW
 #undef ATTN_BODY_CHUNK
 }
 
@@ -1168,7 +1263,8 @@ static int with_head_dim(int64_t d, F &&f) {
 // Hamming(8,4)'s layout only
 template <typename A>
 constexpr bool takes_golay = std::is_same<A, AttnArgs>::value || std::is_same<A, ChunkArgs>::value ||
-                             std::is_same<A, RaggedArgs>::value || std::is_same<A, StatsArgs>::value;
+                             std::is_same<A, RaggedArgs>::value || std::is_same<A, StatsArgs>::value ||
+                             std::is_same<A, WindowArgs>::value;
 // The blocks whose kernels address the caches through buffer descriptors only (caches under 4 GiB)
 template <typename A>
 constexpr bool buf_only = is_interp<A> || is_stats<A> || is_repair<A>;
@@ -1192,6 +1288,8 @@ constexpr auto split_kernel() {
     return &paged_attn_split_kernel<T, CODEC, VEC, W, BUF, G>;
   } else if constexpr (std::is_same<A, RaggedArgs>::value) {
     return &paged_attn_split_chunk_kernel<T, CODEC, VEC, W, BUF, G>;
+  } else if constexpr (std::is_same<A, WindowArgs>::value) {
+    return &paged_attn_split_window_kernel<T, CODEC, VEC, W, BUF, G>;
   } else if constexpr (std::is_same<A, StatsArgs>::value && is_golay(CODEC)) {
     static_assert(BUF, "the counted kernels are buffer-addressed");
     return &paged_attn_split_golay_stats_kernel<T, CODEC, VEC, W, G>;
@@ -1430,6 +1528,8 @@ constexpr auto tile_kernel() {
       return &paged_attn_golay_mfma_chunk_kernel<PACKED>;
     } else if constexpr (std::is_same<A, RaggedArgs>::value) {
       return &paged_attn_golay_mfma_ragged_kernel<PACKED>;
+    } else if constexpr (std::is_same<A, WindowArgs>::value) {
+      return &paged_attn_golay_mfma_window_kernel<PACKED>;
     } else {
       static_assert(std::is_same<A, StatsArgs>::value, "no Golay tile kernel takes this block");
       return &paged_attn_golay_mfma_stats_kernel<PACKED>;
@@ -1438,6 +1538,8 @@ constexpr auto tile_kernel() {
     return &paged_attn_h84_mfma_chunk_kernel<D>;
   } else if constexpr (std::is_same<A, RaggedArgs>::value) {
     return &paged_attn_h84_mfma_ragged_kernel<D>;
+  } else if constexpr (std::is_same<A, WindowArgs>::value) {
+    return &paged_attn_h84_mfma_window_kernel<D>;
   } else if constexpr (std::is_same<A, InterpArgs>::value) {
     return &paged_attn_h84_mfma_interp_kernel<D>;
   } else if constexpr (std::is_same<A, StatsArgs>::value) {
@@ -1675,6 +1777,7 @@ static const char *mode_entry(const AttnMode &m) {
     case AttnKind::golay_counted: return "paged_attention_golay_stats";
     case AttnKind::repair: return "paged_attention_repair";
     case AttnKind::counted: return "paged_attention_stats";
+    case AttnKind::windowed: return "paged_attention_window";
     default: return m.interp ? "paged_attention_interp" : "paged_attention_chunk";
   }
 }
@@ -1684,8 +1787,9 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
   if (c.batch < 0 || c.q_len < 0 || c.heads < 0 || c.kv_heads < 0 || c.head_dim < 0)
     return set_error(KVECC_EINVAL, "paged_attention_chunk: negative size");
   // the mode's legal combinations (the entries have checked their own codec and buffer first)
-  const bool counts = m.kind != AttnKind::plain;
-  if (counts != (m.stats != nullptr) || (m.kind == AttnKind::golay_counted && m.interp))
+  const bool windowed = m.kind == AttnKind::windowed;  // (its entry has checked window >= 1 and sinks >= 0)
+  const bool counts = m.kind != AttnKind::plain && !windowed;
+  if (counts != (m.stats != nullptr) || (m.kind == AttnKind::golay_counted && m.interp) || (windowed && m.interp))
     return set_error(KVECC_EINVAL, "%s: illegal mode (kind %d, interp %d, stats %s)", mode_entry(m), (int)m.kind,
                      (int)m.interp, m.stats ? "set" : "null");
   int codec = c.codec;
@@ -1700,7 +1804,8 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
                      (long long)c.q_sb, (long long)c.q_st, (long long)c.q_sh, (long long)c.head_dim);
   // one token per sequence, [B, H, D] in place: the decode entry, its kernels and its bits
   // (a ragged call stays here: the decode entry knows no spans)
-  if (!m.interp && !counts && !c.q_spans && c.q_len == 1 && (c.heads == 1 || c.q_sh == c.head_dim) &&
+  // (a windowed call stays here too: the decode entry knows no window)
+  if (!m.interp && !counts && !windowed && !c.q_spans && c.q_len == 1 && (c.heads == 1 || c.q_sh == c.head_dim) &&
       (c.batch == 1 || c.q_sb == c.heads * c.head_dim))
     return paged_attention_decode(c);
   const int64_t vbatch = c.batch * c.q_len;  // query rows per head: the virtual batch
@@ -1743,16 +1848,51 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
                                                                : kMfmaWgPerCu),
                        finest);
     // the counted combine as in the decode entry: one query head per workgroup of the split kernels
-    p.ctr = !p.gm && p.gq == 1 && vbatch * c.heads <= kAttnCtrPerSlot;
+    // (a windowed call launches the combine: its empty splits leave before the count)
+    p.ctr = !p.gm && p.gq == 1 && vbatch * c.heads <= kAttnCtrPerSlot && !windowed;
     return (int)KVECC_OK;
   });
   if (rc != KVECC_OK) return rc;
+  // A windowed call plans its grid by the window (WindowArgs): sink_splits splits in place, then
+  // enough to span a workgroup's window from wherever it starts -- window + split - 1 keys, and the
+  // 15 further positions of a tile's later tokens -- at the split size the launcher would pick for a
+  // context of that many keys.  The partials must fit what the contract requires of the workspace --
+  // kvecc_paged_attention_chunk_workspace for this call, the dense plan's bound, NOT the capacity the
+  // caller happens to pass (a cached, grown buffer would otherwise change the plan, and with it the
+  // summation order, from one call to the next): the split doubles until they do.  Where that is no
+  // fewer splits than the dense plan, the dense plan (attn_setup's) stands: sink_splits == nsplit.
+  uint32_t sink_splits = (uint32_t)a.nsplit;
+  if (windowed) {
+    const int64_t need = kvecc_paged_attention_chunk_workspace(
+        c.batch, c.q_len, c.heads, c.head_dim, c.max_context_len <= 0 ? c.max_blocks * c.block_size : c.max_context_len);
+    const int64_t rows = vbatch * c.heads, sinks = std::min<int64_t>(m.sinks, a.ctx_cap);
+    const int64_t span = m.window + (p.gm ? 15 : 0);
+    const int64_t wgs = p.gm ? c.batch * (c.heads / p.gm) * p.tiles : vbatch * c.heads / p.gq;
+    const int per_cu = !p.gm ? 4 : codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu : kMfmaWgPerCu;
+    for (int64_t split = choose_split(wgs, std::min<int64_t>(a.ctx_cap, sinks + span), per_cu);; split <<= 1) {
+      const int64_t ss = cdiv(sinks, split), n = ss + cdiv(span + split - 1, split);
+      if (n >= cdiv(a.ctx_cap, split)) break;
+      if (n <= kMaxSplits && rows * n * (c.head_dim + 2) <= need) {
+        a.split = split;
+        a.nsplit = n;
+        sink_splits = (uint32_t)ss;
+        break;
+      }
+      if (split >= kMaxSplit) break;
+    }
+  }
   hipStream_t st = as_stream(c.stream);
   // the block the mode's kernels take, then its matrix-core tiles or the general path
   auto run = [&](auto b) {
     using B = decltype(b);
     if constexpr (!is_byte<B>) static_cast<RaggedArgs &>(b) = a;
     if constexpr (is_stats<B> || is_repair<B>) b.stats = m.stats;
+    if constexpr (is_window<B>) {  // one block for every codec: the byte table by its selector
+      b.window = (uint32_t)std::min<int64_t>(m.window, 0x7FFFFFFF);
+      b.sinks = (uint32_t)std::min<int64_t>(m.sinks, 0x7FFFFFFF);
+      b.tab = a.tab;
+      b.sink_splits = sink_splits;
+    }
     if (p.gm) return launch_tiles(mode_entry(m), codec, b, c.batch, p.tiles, st);
     return with_q_dtype(mode_entry(m), c.q_dtype, [&](auto t) {
       return launch_rows<typename decltype(t)::type>(mode_entry(m), codec, b, vbatch, p.gq, st);
@@ -1764,6 +1904,7 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
     case AttnKind::golay_counted: lrc = run(StatsArgs{}); break;
     case AttnKind::repair: lrc = m.interp ? run(RepairInterpArgs{}) : run(RepairArgs{}); break;
     case AttnKind::counted: lrc = m.interp ? run(StatsInterpArgs{}) : run(StatsArgs{}); break;
+    case AttnKind::windowed: lrc = run(WindowArgs{}); break;
     default: lrc = m.interp ? run(InterpArgs{}) : bytes ? run(a) : run(RaggedArgs{}); break;
   }
   if (lrc != KVECC_OK) return lrc;
@@ -1846,6 +1987,37 @@ KVECC_API int kvecc_paged_attention_chunk_ragged(const void *query, int64_t q_ba
                                      kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
                                      max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
                                     {});
+}
+
+KVECC_API int kvecc_paged_attention_window(const void *query, int64_t q_batch_stride, int64_t q_token_stride,
+                                           int64_t q_head_stride, int q_dtype, const void *k_cache,
+                                           const void *v_cache, const int32_t *block_table,
+                                           const int32_t *context_lens, const int32_t *q_spans,
+                                           const float *k_scales, const float *v_scales, void *out,
+                                           int64_t batch, int64_t q_max, int64_t heads, int64_t kv_heads,
+                                           int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                           int64_t layer, int64_t block_size, int64_t max_blocks,
+                                           int64_t max_context_len, float sm_scale, int codec, int64_t window,
+                                           int64_t sinks, float *workspace, int64_t workspace_floats,
+                                           void *stream) {
+  if (window < 0 || sinks < 0)
+    return set_error(KVECC_EINVAL, "paged_attention_window: negative window %lld or sinks %lld", (long long)window,
+                     (long long)sinks);
+  // No window, or one that covers every key a row can see (its key limit is at most ctx_cap =
+  // min(max_context_len, max_blocks * block_size)): the plain entry, its kernels and its bits.
+  const int64_t table_cap = max_blocks > 0 && block_size > 0 ? max_blocks * block_size : 0;
+  const int64_t ctx_cap = max_context_len > 0 ? std::min(max_context_len, table_cap) : table_cap;
+  AttnMode m;
+  if (window > 0 && window < ctx_cap) {
+    m.kind = AttnKind::windowed;
+    m.window = window;
+    m.sinks = sinks;
+  }
+  return paged_attention_chunk_impl({query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache,
+                                     block_table, context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads,
+                                     kv_heads, head_dim, num_blocks, num_layers, layer, block_size, max_blocks,
+                                     max_context_len, sm_scale, codec, workspace, workspace_floats, stream},
+                                    m);
 }
 
 KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_stride, int64_t q_token_stride,

@@ -7,6 +7,8 @@
 //     RaggedArgs and its ChunkMap.
 // ATTN_BODY_STATS (paged_attn_golay_mfma_stats_kernel, `a` a StatsArgs, the ragged form): the
 // [statistics] islands.
+// ATTN_BODY_WINDOW (paged_attn_golay_mfma_window_kernel, `a` a WindowArgs, the ragged form over a
+// WindowMap): the [window] islands of the shared fragments, and the loop's first round here.
 // What is Golay's own stands here: the operand maps, the loads and the decode through the spread
 // tables.  Columns, row staging, buffer descriptors, the softmax step and the merge are the
 // Hamming(8,4) body's, one copy each: attn_mfma_columns.inc, attn_mfma_rows.inc,
@@ -97,7 +99,11 @@
   float psum = 0.0f;  // sum of p * v_scale over this lane's tokens (the offset fold)
   float pvc = 0.0f;   // the PV normaliser ([normaliser]); 0: nothing accumulated yet
 
+#ifdef ATTN_BODY_WINDOW  // [window] the rounds before the first visible key are skipped (i_first: whole rounds)
+  for (int i0 = i_first + wave * kMfmaStep; i0 < ntok; i0 += kWaves * kMfmaStep) {
+#else
   for (int i0 = wave * kMfmaStep; i0 < ntok; i0 += kWaves * kMfmaStep) {
+#endif
     int32_t rv[8];
     {
       const int4 r0 = *reinterpret_cast<const int4 *>(&rows[i0 + 4 * g]);

@@ -28,6 +28,10 @@
 // codewords back where it counts them (kvecc.h "Repairing attention"), before the slow path
 // rewrites any in registers -- a double is never stored, and the neighbour words the slow path
 // loads decode to the same nibbles before and after any store.
+// ATTN_BODY_WINDOW (paged_attn_h84_mfma_window_kernel, `a` a WindowArgs, the ragged form over a
+// WindowMap): the [window] islands of the shared fragments -- the column's lower key bound and sink
+// bound at [score mask], the rows no column sees left unstaged, an empty split's early exit -- and
+// the loop's first round here.  Its decode table is Hamming(8,4)'s, Hamming(7,4)'s or INT4's (WindowArgs::tab).
 // Shared with attn_golay_mfma_body.inc, one copy each: attn_mfma_columns.inc, attn_mfma_rows.inc,
 // attn_mfma_descriptors.inc, attn_mfma_softmax.inc, attn_mfma_merge.inc (their headers say what they read
 // and define).
@@ -122,7 +126,11 @@
     }
   };
   constexpr int kStride = kWaves * kMfmaStep;
+#ifdef ATTN_BODY_WINDOW  // [window] the rounds before the first visible key are skipped (i_first: a multiple of kStride)
+  for (int i0 = i_first + wave * kMfmaStep; i0 < ntok; i0 += kStride) {
+#else
   for (int i0 = wave * kMfmaStep; i0 < ntok; i0 += kStride) {
+#endif
     Step cur;
     load_step(i0, cur);
     const int32_t *rv = cur.rv;

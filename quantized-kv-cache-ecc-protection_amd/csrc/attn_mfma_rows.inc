@@ -9,6 +9,8 @@
 //     position t0 + i of the sequence for i in [-1, npad] -- a token on each side of the split's,
 //     bounded by the sequence's length nb, not by the tile's key limit ([score mask] alone masks a
 //     position past every column's limit); -1: no block, or outside [0, nb).
+//   [window] (ATTN_BODY_WINDOW, the windowed kernels) the positions between the sinks and the tile's
+//     smallest lower bound (cm.lo_min) get -1.
 //   [spread tables] (ATTN_ROWS_SPREAD_TABLES, which attn_golay_mfma_body.inc defines around its
 //     inclusion) Golay's decode tables go to gt[] between the slice's loads and their barrier.
 #if ATTN_BODY_CHUNK == 2  // [interpolation] the halo form
@@ -60,7 +62,11 @@
     const int npad = (ntok + kMfmaStep - 1) / kMfmaStep * kMfmaStep;
     for (int i = threadIdx.x; i < npad; i += kBlock) {
       int32_t row = -1;
+#ifdef ATTN_BODY_WINDOW  // [window] a key that no column of the tile sees is a -1 row, as a missing block's
+      if (i < ntok && (t0 + i >= cm.lo_min || t0 + i < (int64_t)a.sinks)) {
+#else
       if (i < ntok) {
+#endif
         const uint32_t pos = (uint32_t)(t0 + i);
         const uint32_t lb = pos / bs;
         const int32_t blk = blks[lb - lb0];

@@ -5,13 +5,18 @@
 // Updates: m, l, psum, pvc, acc[MT] (rescaled to the new pvc).
 // Defines: pb_hi, pb_lo, the PV B operand p * v_scale / pvc as an f16 hi + lo pair (and s, mx, mn, mu,
 // alpha, pw, wmax, ca, cinv, beta, phi, plo on the way).
-// Islands: [score mask] (ATTN_BODY_CHUNK).  A text fragment and not a function: as
+// Islands: [score mask] (ATTN_BODY_CHUNK; ATTN_BODY_WINDOW: also col_lo and col_sink), [window] the
+// masked rows' V scales.  A text fragment and not a function: as
 // pv_softmax_step<MT> it moved the registers of 15 decode kernels (DESIGN.md).
     float s[8];
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-#if ATTN_BODY_CHUNK  // [score mask] col_lim from [key limit]
+#ifdef ATTN_BODY_WINDOW  // [score mask] the windowed kernels: col_lo and col_sink from [window]
+      const int ti = i0 + 16 * (j >> 2) + 4 * g + (j & 3);
+      const bool seen = ti < col_lim && (ti >= col_lo || ti < col_sink);
+      s[j] = rv[j] >= 0 && seen ? (S[j >> 2][j & 3] * kMfmaValScale - qoff) * (qscale * ks[j]) : -INFINITY;
+#elif ATTN_BODY_CHUNK  // [score mask] col_lim from [key limit]
       const bool seen = i0 + 16 * (j >> 2) + 4 * g + (j & 3) < col_lim;
       s[j] = rv[j] >= 0 && seen ? (S[j >> 2][j & 3] * kMfmaValScale - qoff) * (qscale * ks[j]) : -INFINITY;
 #else
@@ -32,8 +37,14 @@
     for (int h = 0; h < 4; ++h) {
       const float p0 = attn_exp(s[2 * h] - mu), p1 = attn_exp(s[2 * h + 1] - mu);
       l += p0 + p1;
+#ifdef ATTN_BODY_WINDOW  // [window] a masked row stands in row 0 of the cache, which may be a released block's: its
+      // weight 0 must not meet a V scale that is no number (0 * NaN)
+      pw[2 * h] = s[2 * h] == -INFINITY ? 0.0f : p0 * vs[2 * h];
+      pw[2 * h + 1] = s[2 * h + 1] == -INFINITY ? 0.0f : p1 * vs[2 * h + 1];
+#else
       pw[2 * h] = p0 * vs[2 * h];
       pw[2 * h + 1] = p1 * vs[2 * h + 1];
+#endif
       psum += pw[2 * h] + pw[2 * h + 1];
       wmax = fmaxf(wmax, fmaxf(pw[2 * h], pw[2 * h + 1]));
     }

@@ -13,6 +13,9 @@
 // The repairing kernels (paged_attn_split_repair*_kernel, `a` a RepairArgs / RepairInterpArgs, Hamming(8,4))
 // define ATTN_BODY_REPAIR besides ATTN_BODY_STATS: the [repair] islands, in which the counting workgroup's
 // live lanes store the corrected codewords of the rows they count (kvecc.h "Repairing attention").
+// The windowed kernels (paged_attn_split_window_kernel, `a` a WindowArgs, ATTN_BODY_CHUNK 1) define
+// ATTN_BODY_WINDOW: the [window] islands -- the row's lower key bound, the empty split's early exit, the
+// -1 rows between sinks and window; without it the preprocessed text is what it was.
   constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
   using C = Chunk<CODEC, VEC>;
   constexpr int E = C::E;
@@ -59,7 +62,14 @@
 #else
   const int64_t ctx = min<int64_t>(a.ctx_lens[b], a.ctx_cap);  // max_context_len and the table
 #endif
+#ifdef ATTN_BODY_WINDOW  // [window] the row's lower key bound; the split's place follows it (WindowArgs::split_start)
+  // The row sits at position p = lim0 + tq - 1 and sees key j < ctx iff j < sinks or j >= lo =
+  // max(p - window + 1, 0) (kvecc.h "Windowed attention").
+  const int64_t lo = row_ok ? max<int64_t>(sp.lim0(a, bt) + tq - (int64_t)a.window, 0) : 0;
+  const int64_t t0 = a.split_start(blockIdx.x, lo);
+#else
   const int64_t t0 = (int64_t)blockIdx.x * a.split;
+#endif
 #ifdef ATTN_BODY_STATS  // [statistics] who counts (kvecc.h "Counted attention"): uniform per workgroup
   // The row of the sequence's last valid token, in the first query-head group of
   // its cache head, counts: one workgroup per (sequence, cache head, split).  It
@@ -82,6 +92,23 @@
   const int cs = live ? c : 0;
   const int64_t ws_stride = a.nsplit * (a.d + 2);  // per query head
   float *ws0 = a.ws + ((b * a.heads + h0) * a.nsplit + blockIdx.x) * (a.d + 2);
+#ifdef ATTN_BODY_WINDOW  // [window] the split's share of the row's visible keys
+  // In this split the row sees the sink keys [t0, min(t1, sinks)) and the window keys
+  // [max(t0, lo), t1).  A split that holds neither -- one past the row's limit included -- reads
+  // no block table and no cache: it writes the empty partial (m = -inf, l = 0, zero
+  // accumulators), which the combine gives no weight, and leaves.
+  const bool sees_sink = min<int64_t>(t1, a.sinks) > t0, sees_win = t1 > max<int64_t>(t0, lo);
+  if (!sees_sink && !sees_win) {  // uniform per workgroup
+    const int nws = (int)a.d + 2;
+    for (int idx = threadIdx.x; idx < G * nws; idx += kBlock) {
+      const int j = idx / nws, e = idx - j * nws;
+      ws_put(ws0 + j * ws_stride + e, e == 0 ? -INFINITY : 0.0f);
+    }
+    return;
+  }
+  // the first pass of the streaming loop that holds a visible key: the passes before it hold -1 rows only
+  const int i_first = sees_sink ? 0 : (int)(max<int64_t>(lo - t0, 0) / (TP * U)) * (TP * U);
+#endif
   // this lane's query slice, issued before the block-table round trip (first
   // used by the query sums after it)
   float qv[G][E];
@@ -125,7 +152,11 @@
     const int npad = (int)a.split + (U - 1) * kBlock;
     for (int i = threadIdx.x; i < npad; i += kBlock) {
       int32_t row = -1;
+#ifdef ATTN_BODY_WINDOW  // [window] a key between the sinks and the window is a -1 row, as a missing block's
+      if (i < ntok && (t0 + i >= lo || t0 + i < (int64_t)a.sinks)) {
+#else
       if (i < ntok) {
+#endif
         const uint32_t pos = (uint32_t)(t0 + i);
         const uint32_t lb = pos / bs;
         const int32_t blk = blks[lb - lb0];
@@ -222,8 +253,13 @@
       }
     }
   };
+#ifdef ATTN_BODY_WINDOW  // [window] the passes before the first visible key are skipped
+  if (kPrefetch && i_first + grp < ntok) load_rows(i_first + grp);
+  for (int i0 = i_first + grp; i0 < ntok; i0 += TP * U) {
+#else
   if (kPrefetch && grp < ntok) load_rows(grp);
   for (int i0 = grp; i0 < ntok; i0 += TP * U) {
+#endif
     if (!kPrefetch) load_rows(i0);
     C kc[U], vc[U];
     float ks[U], vs[U];
@@ -235,6 +271,10 @@
       ks[u] = pks[u];
       vs[u] = pvs[u];
       ok[u] = pok[u];
+#ifdef ATTN_BODY_WINDOW  // [window] a -1 row stands in row 0 of the cache, which may be a released block's:
+      // its weight p = 0 must not meet a V scale that is no number (0 * NaN)
+      if (!ok[u]) vs[u] = 0.0f;
+#endif
     }
     if (kPrefetch && i0 + TP * U < ntok) load_rows(i0 + TP * U);
 #ifdef ATTN_BODY_STATS  // [statistics] the stored bytes of the lane's words, before any interpolation

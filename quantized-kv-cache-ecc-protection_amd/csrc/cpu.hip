@@ -1036,8 +1036,10 @@ void for_each_counted_row(const AttnCall &c, F fn) {
 // INTERP is a template argument so that the byte loop of a call that does not interpolate
 // carries no neighbour test (with the flag read in the loop a plain Hamming(8,4) call
 // takes over twice as long); the results are the same bits either way.
+// window > 0 (a windowed call, kvecc.h "Windowed attention"): the row at position p skips the
+// keys sinks <= j < max(p - window + 1, 0); what it keeps it takes in the same order.
 template <bool INTERP>
-void attention_rows(const AttnCall &c, int threads) {
+void attention_rows(const AttnCall &c, int threads, int64_t window = 0, int64_t sinks = 0) {
   // hot fields into locals: the row loop reads no record
   const void *const query = c.query, *const k_cache = c.k_cache, *const v_cache = c.v_cache;
   const int64_t q_sb = c.q_sb, q_st = c.q_st, q_sh = c.q_sh;
@@ -1112,7 +1114,14 @@ void attention_rows(const AttnCall &c, int threads) {
       auto codewords = [&](const void *cache, int64_t slot) {
         return slot < 0 ? zero_row.data() : reinterpret_cast<const uint8_t *>(cache) + slot * head_dim;
       };
+      // the first key of the row's window (its position is the unclamped key limit - 1)
+      const int64_t lo =
+          valid && window > 0 ? std::max<int64_t>((int64_t)context_lens[b] - count + 1 + (t - first) - window, 0) : 0;
       for (int64_t pos = 0; pos < ctx; ++pos) {
+        if (pos >= sinks && pos < lo) {  // between the sinks and the window: unseen, unread
+          pos = lo - 1;
+          continue;
+        }
         const int64_t srow = slot_of(pos);
         if (srow < 0) continue;
         const int64_t sl = interp ? slot_of(pos > 0 ? pos - 1 : 0) : -1;
@@ -1170,8 +1179,10 @@ int cpu_attention(const char *who, const AttnCall &c, const AttnMode &m, int thr
   const bool decode = !std::strcmp(who, "cpu_paged_attention");
   const bool chunk = !std::strcmp(who, "cpu_paged_attention_chunk");
   const bool ragged = !std::strcmp(who, "cpu_paged_attention_chunk_ragged");
-  const bool counts = m.kind != AttnKind::plain, golay_counts = m.kind == AttnKind::golay_counted;
+  const bool windowed = m.kind == AttnKind::windowed;  // (its entry has checked window and sinks)
+  const bool counts = m.kind != AttnKind::plain && !windowed, golay_counts = m.kind == AttnKind::golay_counted;
   const bool repair = m.kind == AttnKind::repair;
+  if (windowed && m.interp) return set_error(KVECC_EINVAL, "%s: a windowed call does not interpolate", who);
   if (counts && !m.stats) return set_error(KVECC_EINVAL, "%s: null stats", who);
   if (golay_counts && c.codec != KVECC_CODEC_GOLAY && c.codec != KVECC_CODEC_GOLAY_PACKED)
     return set_error(KVECC_EINVAL, "%s: codec %d (this counted twin needs golay or golay_packed)", who, c.codec);
@@ -1211,6 +1222,8 @@ int cpu_attention(const char *who, const AttnCall &c, const AttnMode &m, int thr
     return set_error(KVECC_EINVAL, "cpu_paged_attention: null pointer");
   if (m.interp)
     attention_rows<true>(c, threads);
+  else if (windowed)
+    attention_rows<false>(c, threads, m.window, m.sinks);
   else
     attention_rows<false>(c, threads);
   if (!counts) return KVECC_OK;
@@ -1309,6 +1322,41 @@ KVECC_API int kvecc_cpu_paged_attention_chunk_ragged(const void *query, int64_t 
                         num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
                         nullptr, 0, nullptr},
                        {}, threads);
+}
+
+// Windowed twin (kvecc_paged_attention_window); q_spans may be null.  window 0 or >= ctx_cap: the
+// ragged / chunk twin's bits (the same rows, no key skipped); head_dim is bounded as the device entry's is.
+KVECC_API int kvecc_cpu_paged_attention_window(const void *query, int64_t q_batch_stride,
+                                               int64_t q_token_stride, int64_t q_head_stride, int q_dtype,
+                                               const void *k_cache, const void *v_cache,
+                                               const int32_t *block_table, const int32_t *context_lens,
+                                               const int32_t *q_spans, const float *k_scales,
+                                               const float *v_scales, void *out, int64_t batch,
+                                               int64_t q_max, int64_t heads, int64_t kv_heads,
+                                               int64_t head_dim, int64_t num_blocks, int64_t num_layers,
+                                               int64_t layer, int64_t block_size, int64_t max_blocks,
+                                               int64_t max_context_len, float sm_scale, int codec,
+                                               int64_t window, int64_t sinks, int threads) {
+  if (window < 0 || sinks < 0)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_window: negative window %lld or sinks %lld",
+                     (long long)window, (long long)sinks);
+  if (head_dim > 256)
+    return set_error(KVECC_EINVAL, "cpu_paged_attention_window: head_dim %lld not in [1, 256]", (long long)head_dim);
+  // (as the device entry: a window of ctx_cap keys or more is no window)
+  const int64_t table_cap = max_blocks > 0 && block_size > 0 ? max_blocks * block_size : 0;
+  const int64_t ctx_cap = max_context_len > 0 ? std::min(max_context_len, table_cap) : table_cap;
+  AttnMode m;
+  if (window > 0 && window < ctx_cap) {
+    m.kind = AttnKind::windowed;
+    m.window = window;
+    m.sinks = sinks;
+  }
+  return cpu_attention("cpu_paged_attention_window",
+                       {query, q_batch_stride, q_token_stride, q_head_stride, q_dtype, k_cache, v_cache, block_table,
+                        context_lens, q_spans, k_scales, v_scales, out, batch, q_max, heads, kv_heads, head_dim,
+                        num_blocks, num_layers, layer, block_size, max_blocks, max_context_len, sm_scale, codec,
+                        nullptr, 0, nullptr},
+                       m, threads);
 }
 
 // Interpolating twin (kvecc_paged_attention_interp); q_spans may be null

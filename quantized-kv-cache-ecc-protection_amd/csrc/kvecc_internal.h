@@ -139,13 +139,16 @@ enum class AttnKind {
   golay_counted,  // kvecc_paged_attention_golay_stats: golay / golay_packed, no interpolation
   repair,         // kvecc_paged_attention_repair: the counted call's geometry and argument values
                   // over the repairing kernels, stats[2] too
+  windowed,       // kvecc_paged_attention_window: the ragged call's geometry over the windowed kernels
+                  // (AttnMode::window >= 1, sinks >= 0); no interpolation, no statistics
 };
 struct AttnMode {
   AttnKind kind = AttnKind::plain;
   // Hamming(8,4) caches under 4 GiB through the interpolating kernels at every q_len (q_len 1
   // included: the decode entry's kernels do not interpolate)
   bool interp = false;
-  uint64_t *stats = nullptr;  // every kind but plain: the library's sharded statistics buffer (the twin: a host array)
+  uint64_t *stats = nullptr;  // the counting kinds: the library's sharded statistics buffer (the twin: a host array)
+  int64_t window = 0, sinks = 0;  // windowed: the last `window` keys and the first `sinks` (kvecc.h "Windowed attention")
 };
 
 // ---- device helpers ----------------------------------------------------------

@@ -124,6 +124,9 @@ def _attention_signatures():
                 + [_vp] * 4 + [_vp] * spans + [_vp] * 3  # caches, table, lengths | q_spans | scales, out
                 + [_i64] * 11 + [_f32, _int]  # batch, q_len .. max_context_len | sm_scale, codec
                 + [_int] * interp + [_vp] * stats + tail)
+        # the windowed entry: the ragged entry's list plus (window, sinks) after codec
+        sigs[prefix + "paged_attention_window"] = (
+            [_vp, _i64, _i64, _i64, _int] + [_vp] * 8 + [_i64] * 11 + [_f32, _int] + [_i64, _i64] + tail)
     return sigs
 
 

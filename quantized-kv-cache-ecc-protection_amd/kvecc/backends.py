@@ -33,8 +33,10 @@ FUNCTIONS = (
 # interpolating attention of ECCShimConfig(interp_attention=True);
 # paged_attention_counted_into: the counted attention of counted_attention=True;
 # paged_attention_repair_into: the repairing attention of repair_attention=True).
+# paged_attention_window_into: the sliding-window attention of attention_window=W.
 NATIVE_FUNCTIONS = ("cache_scrub_tensors", "paged_attention_into", "paged_attention_chunk_into",
-                    "paged_attention_counted_into", "paged_attention_repair_into")
+                    "paged_attention_counted_into", "paged_attention_repair_into",
+                    "paged_attention_window_into")
 
 # backend name -> module implementing FUNCTIONS
 CODEC_BACKENDS = {

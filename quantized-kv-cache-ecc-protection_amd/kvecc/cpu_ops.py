@@ -647,7 +647,7 @@ def _host_stats_ptr(stats, n):
 
 def _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
                       layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats, stats_min,
-                      codec_checks=()):
+                      codec_checks=(), window=None):
     """Host twin of ops._call_chunk_entry: the same checks in the same order, a host
     stats buffer of >= stats_min words, and the call of kvecc_cpu_paged_attention_<entry>."""
     from .ops import _check_attention_chunk_args, _check_q_spans, _chunk_entry_args
@@ -662,16 +662,21 @@ def _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens,
     _lib.call("kvecc_cpu_paged_attention_" + entry,
               *_chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, layer_idx, block_size, sm_scale, codec, int(max_context_len or 0), q_spans,
-                                 interp, sp),
+                                 interp, sp, window),
               NUM_THREADS)
     return out
 
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
-                               interp=False, stats=None, repair=False):
+                               interp=False, stats=None, repair=False, window=0, sinks=0):
     """Host twin of ops.paged_attention_chunk_into (same arguments and checks)."""
-    from .ops import _check_interp_codec, _check_stats_codec
+    from .ops import _check_interp_codec, _check_stats_codec, _check_window_args
+    window, sinks = _check_window_args(window, sinks, query.shape[-1], interp, stats, repair)
+    if window:  # kvecc_cpu_paged_attention_window
+        return _call_chunk_entry("window", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, False, None,
+                                 2, window=(window, sinks))
     if repair:
         if stats is None:
             raise ValueError("repair=True needs stats= (a host int64 buffer of >= 3 elements): the repairing "
@@ -685,6 +690,15 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     return _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
                              layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats, 2,
                              checks)
+
+
+def paged_attention_window_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, layer_idx, block_size, sm_scale, codec, window, sinks=0, max_context_len=0,
+                                q_spans=None):
+    """Host twin of ops.paged_attention_window_into (kvecc_cpu_paged_attention_window)."""
+    return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                      out, layer_idx, block_size, sm_scale, codec, max_context_len=max_context_len,
+                                      q_spans=q_spans, window=window, sinks=sinks)
 
 
 def paged_attention_repair_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,

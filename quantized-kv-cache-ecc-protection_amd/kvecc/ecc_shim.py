@@ -167,6 +167,26 @@ class ECCShimConfig:
     accumulate in get_ecc_repaired(model).  A sequence held at count 0 is neither
     read nor repaired, and the other codecs, layers that are not being read and
     the scales still need the scrubber.
+    ``attention_window`` = W > 0 (append mode, all four append codecs, opt-in)
+    is sliding-window attention with ``attention_sinks`` = S sink tokens: a
+    query at position p sees the keys j <= p with j > p - W or j < S.
+    Positions stay absolute -- Mistral-style masking over the stored, post-RoPE
+    keys; nothing in the cache is re-indexed.  Every forward
+    of ``_append_attend`` goes through kvecc_paged_attention_window when
+    head_dim <= 256, with or without held spans; above that the read + SDPA
+    path applies the same rule in its mask.  Plain attention only: a window
+    raises ValueError together with use_interpolation, decode_stats,
+    interp_attention, stats_attention, counted_attention or repair_attention.
+    ``evict_blocks`` (needs a window) gives blocks that no future query can see
+    back to the pool before every forward, so a sequence keeps about S + W
+    tokens resident however long it runs (SimpleBlockManager.evict;
+    evict_ecc_cache(model) does it on request).  Eviction is host work -- it
+    edits the manager's lists and uploads the released ids -- so
+    ``evict_blocks`` is not for forwards captured in a HIP graph: a replay
+    skips the host logic (and the host lengths the rule reads), so nothing is
+    evicted; use it with eager forwards.  The block table stays
+    num_blocks columns wide: a sequence can reach num_blocks * block_size
+    logical tokens.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -178,7 +198,8 @@ class ECCShimConfig:
                  inject_errors=False, seed=42, use_interpolation=False, backend="hip",
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
                  decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False,
-                 stats_attention=False, counted_attention=False, repair_attention=False):
+                 stats_attention=False, counted_attention=False, repair_attention=False,
+                 attention_window=0, attention_sinks=0, evict_blocks=False):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -228,6 +249,23 @@ class ECCShimConfig:
             raise ValueError("repair_attention=True needs cache_mode='append' and codec='hamming84', "
                              f"not codec={codec!r}, cache_mode={cache_mode!r}")
         self.repair_attention = bool(repair_attention)
+        for name, v in (("attention_window", attention_window), ("attention_sinks", attention_sinks)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be an int >= 0, got {v!r}")
+        if attention_window:
+            if cache_mode != "append":
+                raise ValueError("attention_window needs cache_mode='append'")
+            clash = [n for n, on in (("use_interpolation", use_interpolation), ("decode_stats", decode_stats),
+                                     ("interp_attention", interp_attention), ("stats_attention", stats_attention),
+                                     ("counted_attention", counted_attention),
+                                     ("repair_attention", repair_attention)) if on]
+            if clash:
+                raise ValueError(f"attention_window is plain attention only: it does not go with {', '.join(clash)}")
+        if evict_blocks and not attention_window:
+            raise ValueError("evict_blocks=True needs attention_window > 0: without a window every block stays visible")
+        self.attention_window = int(attention_window)
+        self.attention_sinks = int(attention_sinks)
+        self.evict_blocks = bool(evict_blocks)
 
 
 class SimpleBlockManager:
@@ -324,7 +362,7 @@ class SimpleBlockManager:
     def free(self, seq_id):
         """Return seq_id's blocks, zeroed: zero codewords decode clean, so a
         re-used block adds no stale statistics."""
-        blocks = self.seq_to_blocks.pop(seq_id, [])
+        blocks = [x for x in self.seq_to_blocks.pop(seq_id, []) if x >= 0]  # (evicted positions hold -1)
         self.seq_to_len.pop(seq_id, None)
         self._host_table.pop(seq_id, None)
         if blocks:
@@ -338,10 +376,43 @@ class SimpleBlockManager:
         for row in self._host_lens:
             row[seq_id] = 0
 
+    def evict(self, seq_id, window, sinks):
+        """Release the blocks of seq_id that no future query can see under a
+        sliding window of `window` keys with `sinks` sink tokens; returns how many.
+
+        Lmin is the smallest length of the sequence over all layers (host mirror):
+        every query still to come sits at a position >= Lmin.  Logical block lb
+        is releasable iff lb * bs >= sinks (it holds no sink token) and
+        (lb + 1) * bs - 1 <= Lmin - window (its last token lies before the window
+        of position Lmin, hence of every later one).  A released block is zeroed
+        as free() zeroes it and goes back to the sorted free list; its table
+        entry becomes -1, which every kernel skips, and seq_to_blocks /
+        _host_table keep a -1 at its logical position, so allocate() goes on
+        counting logical blocks."""
+        blocks = self.seq_to_blocks.get(seq_id)
+        if not blocks or window <= 0:
+            return 0
+        bs = self.block_size
+        lmin = min(row[seq_id] for row in self._host_lens)
+        first = -(-sinks // bs)  # the first block that holds no sink token
+        end = min((lmin - window + 1) // bs, len(blocks))  # exclusive: (lb + 1) * bs <= lmin - window + 1
+        gone = [blocks[lb] for lb in range(first, end) if blocks[lb] >= 0]
+        if not gone:  # nothing new: no device work
+            return 0
+        for lb in range(first, end):
+            blocks[lb] = -1
+        idx = torch.tensor(gone, dtype=torch.long, device=self.k_cache.device)
+        for t in (self.k_cache, self.v_cache, self.k_scales, self.v_scales):
+            t[idx] = 0
+        self.free_blocks.extend(gone)
+        self.free_blocks.sort()
+        self.block_table[seq_id, first:end].fill_(-1)
+        return len(gone)
+
     def allocate(self, seq_id, num_tokens):
         need = (num_tokens + self.block_size - 1) // self.block_size
         existing = self.seq_to_blocks.get(seq_id, [])
-        new_needed = max(0, need - len(existing))
+        new_needed = max(0, need - len(existing))  # logical blocks: evicted positions stay in the list as -1
         if new_needed > len(self.free_blocks):
             raise RuntimeError(f"Out of blocks: need {new_needed}, have {len(self.free_blocks)}")
         new = [self.free_blocks.pop(0) for _ in range(new_needed)]
@@ -371,7 +442,7 @@ class SimpleBlockManager:
         # specialises a traced forward's allocation on the free list, and a
         # rotating list recompiled the patched model on every forward
         for blocks in self.seq_to_blocks.values():
-            self.free_blocks.extend(blocks)
+            self.free_blocks.extend(x for x in blocks if x >= 0)  # (evicted positions hold -1)
         self.free_blocks.sort()
         self.seq_to_blocks.clear()
         self.seq_to_len.clear()
@@ -665,7 +736,13 @@ class ECCBackend:
             raise TypeError(f"append mode: K/V dtype {k.dtype}/{v.dtype} has no fused write")
         d, hk = self.head_dim, self.num_kv_heads
         if self._spans is not None:
-            self._check_spans(batch, q_len)  # before anything is written
+            self._check_spans(batch, q_len)  # before anything is written or released
+        if getattr(cfg, "evict_blocks", False) and layer_idx == 0:
+            # before the forward's first write (and after every check that can refuse the forward),
+            # when every layer holds the same lengths: the blocks no query from here on can see go
+            # back to the pool this forward allocates from.  Host work: not for a captured forward.
+            self.evict()
+        if self._spans is not None:
             counts = self._spans[0]
             total = sum(counts)
             self._total_values += 2 * total * hk * d
@@ -702,6 +779,17 @@ class ECCBackend:
         if inject:
             self._injection_count += batch * q_len * hk
 
+    def evict(self):
+        """Release every live sequence's blocks that lie behind its sliding window
+        and hold no sink token (SimpleBlockManager.evict: the rule, from the host
+        lengths of all layers); returns the number of blocks released."""
+        cfg = self.config
+        window, sinks = getattr(cfg, "attention_window", 0), getattr(cfg, "attention_sinks", 0)
+        if not window:
+            raise ValueError("eviction needs ECCShimConfig(attention_window > 0): without a window every block "
+                             "stays visible")
+        return sum(self.manager.evict(seq, window, sinks) for seq in list(self.manager.seq_to_blocks))
+
     def _append_attend(self, q, layer_idx):
         """Attention of q [batch, heads, q_len, head_dim], row b over sequence
         b's own cache; the layer's write has already advanced the lengths."""
@@ -715,6 +803,27 @@ class ECCBackend:
         interp = cfg.use_interpolation and cfg.codec == "hamming84"
         # hamming74 / int4 take the kernels only under kernel_attention (their codec is checked there)
         kernel_codec = cfg.codec in ("hamming84", "golay") or cfg.kernel_attention
+        window, sinks = getattr(cfg, "attention_window", 0), getattr(cfg, "attention_sinks", 0)
+        if window and d <= 256:
+            # every q_len and every append codec on the windowed kernels: q read in place as
+            # [batch, q_len, heads, d]; row at p sees keys j <= p with j > p - window or j < sinks
+            sp = None
+            if self._spans is not None:
+                self._check_spans(b, q_len)
+                sp = self._span_buf[:b]
+            qt = q.transpose(1, 2)
+            if self._traced():
+                out = torch.ops.kvecc.paged_attention_window(
+                    qt, mgr.k_cache, mgr.v_cache, table, dev_lens, sp, mgr.k_scales, mgr.v_scales, layer_idx,
+                    mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, window, sinks, ctx)
+                return out.transpose(1, 2)
+            if not hasattr(self.codec_backend, "paged_attention_window_into"):
+                raise ValueError("attention_window needs a backend with paged_attention_window_into")
+            out = torch.empty(qt.shape, dtype=q.dtype, device=q.device)
+            self.codec_backend.paged_attention_window_into(
+                qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
+                mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, window, sinks, max_context_len=ctx, q_spans=sp)
+            return out.transpose(1, 2)
         if cfg.counted_attention and cfg.codec == "golay" and d <= 256:
             # every q_len on the Golay counted kernels (int32 or packed rows): the bits
             # corrected / uncorrectable words of the codewords read added to the shim's buffer
@@ -853,10 +962,15 @@ class ECCBackend:
             first, count = spans[:, 0].view(b, 1, 1), spans[:, 1].view(b, 1, 1)
             valid = (tq >= first) & (tq < first + count)
             qpos = (dev_lens.view(b, 1, 1) - count) + (tq - first)
-            mask = torch.where(valid, keys <= qpos, keys == 0)
+            seen = keys <= qpos
+            if window:  # (head_dim > 256) the windowed rule of the kernels, in the mask
+                seen = seen & ((keys > qpos - window) | (keys < sinks))
+            mask = torch.where(valid, seen, keys == 0)
             return F.scaled_dot_product_attention(q, k_t, v_t, attn_mask=mask.unsqueeze(1))
         qpos = (dev_lens - q_len).view(b, 1, 1) + tq
         mask = keys <= qpos
+        if window:  # (head_dim > 256) the windowed rule of the kernels, in the mask
+            mask = mask & ((keys > qpos - window) | (keys < sinks))
         return F.scaled_dot_product_attention(q, k_t, v_t, attn_mask=mask.unsqueeze(1))
 
     def _traced(self):
@@ -1266,7 +1380,7 @@ def get_ecc_stats(model):
     stats = {}
     if hasattr(model, "_ecc_block_manager"):
         m = model._ecc_block_manager
-        stats["allocated_blocks"] = sum(len(b) for b in m.seq_to_blocks.values())
+        stats["allocated_blocks"] = sum(sum(1 for x in b if x >= 0) for b in m.seq_to_blocks.values())
         stats["free_blocks"] = len(m.free_blocks)
         stats["sequences"] = len(m.seq_to_blocks)
     if hasattr(model, "_ecc_backend"):
@@ -1311,6 +1425,21 @@ def scrub_ecc_cache(model, layers=None):
     before = be.scrub_totals()
     be.scrub(layers)
     return dict(zip(_SCRUB_KEYS, (int(x) for x in (be.scrub_totals() - before).tolist())))
+
+
+def evict_ecc_cache(model):
+    """Give the blocks that no future query can see under the config's sliding
+    window back to the pool (ECCShimConfig(attention_window=W, attention_sinks=S);
+    no reference counterpart) and return how many were released.  With Lmin a
+    sequence's smallest length over all layers, logical block lb goes iff
+    lb * block_size >= S and (lb + 1) * block_size - 1 <= Lmin - W: it is zeroed,
+    returned to the sorted free list, and its block-table entry becomes -1, which
+    the attention kernels, the scrubber and the batched read all skip.  Call it
+    between forwards; ECCShimConfig(evict_blocks=True) does so before every
+    forward's first write.  ValueError without a window."""
+    if not hasattr(model, "_ecc_backend"):
+        raise ValueError("model is not patched with patch_model_with_ecc_attention")
+    return model._ecc_backend.evict()
 
 
 def age_ecc_cache(model, ber, seed):

@@ -1236,11 +1236,29 @@ def _check_stats_codec(codec):
         raise ValueError(f"stats needs hamming84 (the counted attention kernels), got codec {codec!r}")
 
 
+def _check_window_args(window, sinks, head_dim, interp=False, stats=None, repair=False):
+    """The windowed call's own arguments (both backends): window >= 0 (0: no
+    window) and sinks >= 0 as ints; a window goes with plain attention only and
+    with head_dim <= 256 (kvecc.h "Windowed attention").  Returns them as ints."""
+    for name, v in (("window", window), ("sinks", sinks)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int, got {type(v).__name__}")
+        if v < 0:
+            raise ValueError(f"{name} must be >= 0, got {v}")
+    if window:
+        if interp or stats is not None or repair:
+            raise ValueError("a window goes with plain attention only: no interp, stats or repair")
+        if head_dim > 256:
+            raise ValueError(f"windowed attention needs head_dim <= 256, got {head_dim}")
+    return int(window), int(sinks)
+
+
 def _chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
-                      layer_idx, block_size, sm_scale, codec, mcl, q_spans, interp, sp):
+                      layer_idx, block_size, sm_scale, codec, mcl, q_spans, interp, sp, window=None):
     """A chunk-family entry's arguments up to its workspace (the GPU entries) or
-    its thread count (the host twins); sp: the stats pointer."""
-    takes_spans, takes_interp, takes_stats = _CHUNK_ENTRY_EXTRAS[entry]
+    its thread count (the host twins); sp: the stats pointer; window: the
+    windowed entry's (window, sinks), after codec."""
+    takes_spans, takes_interp, takes_stats = (True, False, False) if entry == "window" else _CHUNK_ENTRY_EXTRAS[entry]
     batch, q_len, heads, head_dim = query.shape
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     args = [_ptr(query), query.stride(0), query.stride(1), query.stride(2), _DT[query.dtype], _ptr(k_cache),
@@ -1254,12 +1272,14 @@ def _chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens,
         args.append(int(bool(interp)))
     if takes_stats:
         args.append(sp)
+    if entry == "window":
+        args += [int(window[0]), int(window[1])]
     return args
 
 
 def _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales, out,
                       layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, interp, stats,
-                      codec_checks=()):
+                      codec_checks=(), window=None):
     """The shared work of the chunk-family entries: the argument checks (then the
     caller's codec_checks, each called with the codec), the stats pointer, the
     spans, the cached workspace, and the call of kvecc_paged_attention_<entry>."""
@@ -1278,14 +1298,14 @@ def _call_chunk_entry(entry, query, k_cache, v_cache, block_table, context_lens,
     ws = _attn_workspace(query.device, ws_n)
     _lib.call("kvecc_paged_attention_" + entry,
               *_chunk_entry_args(entry, query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
-                                 out, layer_idx, block_size, sm_scale, codec, mcl, q_spans, interp, sp),
+                                 out, layer_idx, block_size, sm_scale, codec, mcl, q_spans, interp, sp, window),
               _ptr(ws), ws.numel(), _stream(query.device))
     return out
 
 
 def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                out, layer_idx, block_size, sm_scale, codec, max_context_len=0, q_spans=None,
-                               interp=False, stats=None, repair=False):
+                               interp=False, stats=None, repair=False, window=0, sinks=0):
     """kvecc_paged_attention_chunk: q_len query tokens per sequence, causal (include/kvecc.h).
 
     query [B, q_len, H, D] with any strides and a unit innermost one (the
@@ -1316,7 +1336,17 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     the counted call's output and counts, and k_cache / v_cache are MUTATED in
     place -- every correctable non-canonical byte the call counts is rewritten
     as cache_scrub_tensors would, stats[2] += bytes rewritten
-    (paged_attention_repair_into)."""
+    (paged_attention_repair_into).
+
+    window=W > 0 (kvecc_paged_attention_window; every codec, plain attention
+    only, head_dim <= 256): a query row at position p sees the last W keys up to
+    and including p plus the first ``sinks`` keys, positions absolute; with or
+    without q_spans, q_len 1 included.  window=0: no window, sinks ignored."""
+    window, sinks = _check_window_args(window, sinks, query.shape[-1], interp, stats, repair)
+    if window:
+        return _call_chunk_entry("window", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                 out, layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, False, None,
+                                 window=(window, sinks))
     if repair:
         if stats is None:
             raise ValueError("repair=True needs stats= (an ops.new_stats buffer): the repairing kernels count")
@@ -1333,13 +1363,14 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
 
 def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                           layer_idx, block_size, sm_scale=None, codec="hamming84", max_context_len=0,
-                          q_spans=None, interp=False, stats=None, repair=False):
+                          q_spans=None, interp=False, stats=None, repair=False, window=0, sinks=0):
     """paged_attention_chunk_into with a fresh [B, q_len, H, D] output; on the
     GPU or, for host tensors, through the host twin.  q_spans: a ragged call;
     interp: double errors interpolated (hamming84); stats: the counted kernels
     (hamming84), decode statistics added to the buffer; repair (with stats):
     the repairing kernels, which also rewrite the correctable bytes they count
-    in k_cache / v_cache."""
+    in k_cache / v_cache; window / sinks: sliding-window attention with sink
+    tokens (every codec, plain attention only)."""
     if sm_scale is None:
         sm_scale = 1.0 / math.sqrt(query.shape[-1])
     out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
@@ -1348,11 +1379,23 @@ def paged_attention_chunk(query, k_cache, v_cache, block_table, context_lens, k_
         return cpu_ops.paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
                                                   v_scales, out, layer_idx, block_size, sm_scale, codec,
                                                   max_context_len=max_context_len, q_spans=q_spans,
-                                                  interp=interp, stats=stats, repair=repair)
+                                                  interp=interp, stats=stats, repair=repair, window=window,
+                                                  sinks=sinks)
     return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                       out, layer_idx, block_size, sm_scale, codec,
                                       max_context_len=max_context_len, q_spans=q_spans, interp=interp,
-                                      stats=stats, repair=repair)
+                                      stats=stats, repair=repair, window=window, sinks=sinks)
+
+
+def paged_attention_window_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                out, layer_idx, block_size, sm_scale, codec, window, sinks=0, max_context_len=0,
+                                q_spans=None):
+    """kvecc_paged_attention_window (include/kvecc.h "Windowed attention"):
+    paged_attention_chunk_into(window=, sinks=) under a name of its own, the
+    backend registry's entry for the shim.  window 0 is the plain call."""
+    return paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
+                                      out, layer_idx, block_size, sm_scale, codec, max_context_len=max_context_len,
+                                      q_spans=q_spans, window=window, sinks=sinks)
 
 
 def _check_repair_codec(codec):

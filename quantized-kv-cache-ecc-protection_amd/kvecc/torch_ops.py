@@ -436,6 +436,28 @@ def _(query, k_cache, v_cache, block_table, context_lens, q_spans, k_scales, v_s
     return query.new_empty(query.shape)
 
 
+@torch.library.custom_op("kvecc::paged_attention_window", mutates_args=(), device_types=_DEV)
+def paged_attention_window(query: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor,
+                           context_lens: Tensor, q_spans: Optional[Tensor], k_scales: Tensor, v_scales: Tensor,
+                           layer_idx: int, block_size: int, sm_scale: float, codec: str, window: int,
+                           sinks: int = 0, max_context_len: int = 0) -> Tensor:
+    """Sliding-window paged attention with sink tokens (kvecc_paged_attention_window):
+    a row at position p sees the last ``window`` keys up to p and the first
+    ``sinks`` keys.  query [B, q_max, H, D], q_max 1 the decode step; q_spans
+    None: a uniform call; window 0: the plain call."""
+    out = torch.empty(query.shape, dtype=query.dtype, device=query.device)
+    _be(query).paged_attention_window_into(query, k_cache, v_cache, block_table, context_lens, k_scales,
+                                           v_scales, out, layer_idx, block_size, sm_scale, codec, window, sinks,
+                                           max_context_len=max_context_len, q_spans=q_spans)
+    return out
+
+
+@paged_attention_window.register_fake
+def _(query, k_cache, v_cache, block_table, context_lens, q_spans, k_scales, v_scales, layer_idx, block_size,
+      sm_scale, codec, window, sinks=0, max_context_len=0):
+    return query.new_empty(query.shape)
+
+
 @torch.library.custom_op("kvecc::paged_attention_stats", mutates_args=("stats",), device_types=_DEV)
 def paged_attention_stats(query: Tensor, k_cache: Tensor, v_cache: Tensor, block_table: Tensor,
                           context_lens: Tensor, q_spans: Optional[Tensor], k_scales: Tensor, v_scales: Tensor,
@@ -510,5 +532,5 @@ OPS: List[str] = ["hamming74_encode", "hamming84_encode", "hamming74_decode", "h
                   "fused_quantize_encode", "fused_decode_dequantize_hamming84", "shim_write", "shim_append",
                   "shim_append_ragged", "shim_read", "cache_scrub", "paged_attention", "paged_attention_chunk",
                   "paged_attention_chunk_ragged", "paged_attention_interp", "paged_attention_stats",
-                  "paged_attention_golay_stats", "paged_attention_repair"]
+                  "paged_attention_golay_stats", "paged_attention_repair", "paged_attention_window"]
 _ = _lib  # the operators bind libkvecc.so lazily, on first call

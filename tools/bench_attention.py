@@ -50,6 +50,12 @@ the pair it replaces -- with the dirty cache restored by a device copy before EV
 outside that call's event pair (the repairing call cleans what it reads); and the second, now
 clean, repairing call.
 
+--window times the windowed entry (kvecc_paged_attention_window) in one process: fp16, --heads
+query heads over --heads / 4 cache heads, hamming84 and golay_packed, a decode step and a 16-token
+chunk, W = 1024 and S = 4 at --ctx (run it at 4096 and 32768), one JSON line per case, medians of
+--passes passes that visit the legs in turn: (a) the unwindowed call at ctx, (b) the unwindowed call
+over the same cache at ctx = S + W -- the floor for (c) -- and (c) the windowed call at ctx.
+
 --pkg DIR imports kvecc from DIR instead of this tree (the same measurement on
 another build, e.g. the parent commit's, in the same session).
 """
@@ -110,6 +116,8 @@ def main():
                     help="the counted entry beside the uncounted kernels and the counting read + SDPA")
     ap.add_argument("--repair", action="store_true",
                     help="the repairing entry beside the counted entry and the counted entry + cache_scrub")
+    ap.add_argument("--window", action="store_true",
+                    help="the windowed entry (W 1024, S 4) beside the unwindowed call at ctx and at ctx = S + W")
     ap.add_argument("--pkg", default=None, help="directory to import kvecc from (default: this tree)")
     args = ap.parse_args()
     if args.pkg:
@@ -122,6 +130,8 @@ def main():
         return bench_bytes(args, ops, dev)
     if args.repair:
         return bench_repair(args, ops, dev)
+    if args.window:
+        return bench_window(args, ops, dev)
     if args.stats:
         return bench_stats(args, ops, dev)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -684,6 +694,70 @@ def bench_repair(args, ops, dev):
                                   "block_size": args.bs, "interp": interp, "dirty_ber": 1e-3,
                                   "dirty_counts_per_call": got, **res}), flush=True)
         del kc, vc, x, clean, dirty
+
+
+def bench_window(args, ops, dev):
+    import statistics
+    import time
+
+    from kvecc.memory_layout import kv_cache_pair
+    window, sinks = 1024, 4
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    kvh = max(1, args.heads // 4)
+    sm = 1 / math.sqrt(args.d)
+    short = sinks + window  # leg (b): what a windowed row sees at most
+
+    def warm(fn):
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 >= args.warmup_s:
+                break
+
+    for codec in ("hamming84", "golay_packed"):
+        per = args.d if codec == "hamming84" else (3 * ((args.d + 2) // 3) + 3) // 4 * 4
+        kc, vc = kv_cache_pair((blocks, 1, kvh, args.bs * per), torch.uint8, dev)
+        for c in (kc, vc):  # random bytes: every codeword through the full correction path
+            c.copy_(torch.randint(0, 256, c.shape, device=dev, generator=g, dtype=torch.uint8))
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        lens_short = torch.full((args.batch,), short, dtype=torch.int32, device=dev)
+        for n in (1, 16):
+            qt = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half().transpose(1, 2)
+            out = torch.empty(qt.shape, dtype=qt.dtype, device=dev)
+
+            def call(ln, mcl, **kw):
+                return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, ln, ks, vs, out, 0, args.bs, sm, codec,
+                                                              mcl, **kw)
+
+            cases = {"a_unwindowed": call(lens, args.ctx), "b_unwindowed_at_s_plus_w": call(lens_short, short),
+                     "c_windowed": call(lens, args.ctx, window=window, sinks=sinks)}
+            cases["c_windowed"]()
+            assert bool(out.isfinite().all())
+            for fn in cases.values():
+                warm(fn)
+            passes = {name: [] for name in cases}
+            for _ in range(args.passes):
+                for name, fn in cases.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.iters):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    passes[name].append(e0.elapsed_time(e1) / args.iters * 1e3)
+            res = {name: {"us_per_call": round(statistics.median(p), 2), "pass_us": [round(x, 2) for x in p]}
+                   for name, p in passes.items()}
+            print(json.dumps({"kernel": "paged_attention_window", "codec": codec, "batch": args.batch, "q_len": n,
+                              "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
+                              "block_size": args.bs, "window": window, "sinks": sinks, **res}), flush=True)
+        del kc, vc, ks, vs
 
 
 def bench_golay_stats(args, ops, dev):
