@@ -187,6 +187,15 @@ class ECCShimConfig:
     evicted; use it with eager forwards.  The block table stays
     num_blocks columns wide: a sequence can reach num_blocks * block_size
     logical tokens.
+    The size condition: the interpolating, counted and repairing kernels
+    (``interp_attention``, ``stats_attention``, ``counted_attention``,
+    ``repair_attention``) address the caches with 32-bit buffer offsets, so beside
+    head_dim <= 256 those routes need each cache, and each scale array, under
+    4 GiB (SimpleBlockManager.fits_buffer_kernels, from num_blocks and the
+    model's shape).  Over a larger pool they fall back exactly as above head_dim
+    256: the read + SDPA path, decode_stats=True's statistics, interpolation in
+    the read, nothing repaired.  The plain, windowed and ``kernel_attention``
+    routes have 64-bit-addressed kernels and do not depend on the size.
     The error counts those paths do not keep are a by-product of
     scrub_ecc_cache(model), which also repairs the resident codewords in place.
     """
@@ -313,6 +322,10 @@ class SimpleBlockManager:
         sshape = (num_blocks, num_layers, num_kv_heads, block_size)
         self.k_scales = torch.zeros(sshape, dtype=torch.float32, device=device)
         self.v_scales = torch.zeros(sshape, dtype=torch.float32, device=device)
+        # whether the paged attention kernels address these caches through buffer descriptors
+        # (the interpolating, counted and repairing kernels exist in that form only)
+        self.buffer_addressable = self.fits_buffer_kernels(
+            num_blocks, num_layers, num_kv_heads, block_size, head_dim, codec, golay_storage)
         self.free_blocks = list(range(num_blocks))
         self.seq_to_blocks = {}
         self.seq_to_len = {}
@@ -331,6 +344,23 @@ class SimpleBlockManager:
         # context_lens) with a host mirror (allocation, max_context_len)
         self.ctx_lens = torch.zeros((num_layers, self.max_seqs), dtype=torch.int32, device=device)
         self._host_lens = [[0] * self.max_seqs for _ in range(num_layers)]
+
+    @staticmethod
+    def fits_buffer_kernels(num_blocks, num_layers, num_kv_heads, block_size, head_dim, codec="hamming84",
+                            golay_storage="int32"):
+        """True iff a cache of this shape and storage is under the 4 GiB switch of
+        the paged attention entries (csrc/attention.hip, attn_setup's `fits`): one
+        cache's bytes and one scale array's bytes (4 per token row) both fit 32 bits.
+        Below it the kernels use 32-bit buffer offsets; at and above it only the
+        plain, windowed and byte-codec entries have kernels, and the interpolating,
+        counted and repairing entries return KVECC_EINVAL."""
+        rows = num_blocks * num_layers * num_kv_heads * block_size
+        if codec == "golay":
+            g = (head_dim + 2) // 3
+            row_bytes = golay_packed_row_bytes(g) if golay_storage == "packed" else 4 * g
+        else:  # one byte per value (int4, hamming74, hamming84)
+            row_bytes = head_dim
+        return rows * row_bytes <= 0xFFFFFFFF and rows * 4 <= 0xFFFFFFFF
 
     # ---- append mode: per-sequence, per-layer lengths ----------------------------
     def layer_lens(self, layer, batch):
@@ -804,6 +834,13 @@ class ECCBackend:
         # hamming74 / int4 take the kernels only under kernel_attention (their codec is checked there)
         kernel_codec = cfg.codec in ("hamming84", "golay") or cfg.kernel_attention
         window, sinks = getattr(cfg, "attention_window", 0), getattr(cfg, "attention_sinks", 0)
+        # The interpolating, counted and repairing entries have buffer-addressed kernels only
+        # (caches under 4 GiB: SimpleBlockManager.fits_buffer_kernels).  On a larger cache those
+        # routes fall back as they do above head_dim 256: a counting route to the read + SDPA
+        # path, which counts what decode_stats=True counts (and repairs nothing), the
+        # interpolating one to the read + SDPA path, which interpolates in the read.
+        sized = d <= 256 and getattr(mgr, "buffer_addressable", True)  # (a manager of the caller's own: as before)
+        counting = cfg.decode_stats or cfg.stats_attention or cfg.counted_attention or cfg.repair_attention
         if window and d <= 256:
             # every q_len and every append codec on the windowed kernels: q read in place as
             # [batch, q_len, heads, d]; row at p sees keys j <= p with j > p - window or j < sinks
@@ -824,7 +861,7 @@ class ECCBackend:
                 qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, window, sinks, max_context_len=ctx, q_spans=sp)
             return out.transpose(1, 2)
-        if cfg.counted_attention and cfg.codec == "golay" and d <= 256:
+        if cfg.counted_attention and cfg.codec == "golay" and sized:
             # every q_len on the Golay counted kernels (int32 or packed rows): the bits
             # corrected / uncorrectable words of the codewords read added to the shim's buffer
             sp = None
@@ -842,7 +879,7 @@ class ECCBackend:
                 qt, mgr.k_cache, mgr.v_cache, table, dev_lens, mgr.k_scales, mgr.v_scales, out, layer_idx,
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, self._stats, max_context_len=ctx, q_spans=sp)
             return out.transpose(1, 2)
-        if cfg.repair_attention and d <= 256:
+        if cfg.repair_attention and sized:
             # the counted route below on the repairing kernels: the same outputs and counts, and
             # the correctable bytes read are rewritten in mgr.k_cache / mgr.v_cache in place
             sp = None
@@ -861,7 +898,7 @@ class ECCBackend:
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, self._stats, max_context_len=ctx, q_spans=sp,
                 interp=interp)
             return out.transpose(1, 2)
-        if (cfg.stats_attention or cfg.counted_attention) and d <= 256:  # (counted_attention: hamming84 here)
+        if (cfg.stats_attention or cfg.counted_attention) and sized:  # (counted_attention: hamming84 here)
             # every q_len on the counted kernels: q read in place as [batch, q_len,
             # heads, d], the decode statistics of the bytes read added to the shim's
             # buffer, doubles interpolated inline iff use_interpolation
@@ -881,7 +918,7 @@ class ECCBackend:
                 mgr.block_size, 1.0 / math.sqrt(d), mgr.shim_codec, max_context_len=ctx, q_spans=sp,
                 interp=interp, stats=self._stats)
             return out.transpose(1, 2)
-        if q_len == 1 and kernel_codec and not interp and not cfg.decode_stats and d <= 256:
+        if q_len == 1 and kernel_codec and not interp and not counting and d <= 256:
             # decode step: paged attention with inline decode over the ragged
             # tables; no statistics, as on the reference's seq_len == 1 path
             q1 = q[:, :, 0, :].contiguous()
@@ -899,7 +936,7 @@ class ECCBackend:
         if self._spans is not None:
             self._check_spans(b, q_len)
             spans = self._span_buf[:b]
-        if interp and cfg.interp_attention and not cfg.decode_stats and d <= 256:
+        if interp and cfg.interp_attention and not counting and sized:
             # every q_len on the interpolating kernel: q read in place as [batch,
             # q_len, heads, d], doubles interpolated inline, no dense K / V, no statistics
             qt = q.transpose(1, 2)
@@ -915,7 +952,7 @@ class ECCBackend:
                 interp=True)
             return out.transpose(1, 2)
         chunk_kernel = cfg.kernel_attention or (cfg.chunk_attention and cfg.codec in ("hamming84", "golay"))
-        if q_len > 1 and chunk_kernel and not interp and not cfg.decode_stats and d <= 256:
+        if q_len > 1 and chunk_kernel and not interp and not counting and d <= 256:
             # prefill / chunk / verify step on the chunked causal kernel: q read
             # in place as [batch, q_len, heads, d], no dense K / V, no statistics
             qt = q.transpose(1, 2)

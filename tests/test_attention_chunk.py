@@ -44,26 +44,26 @@ LAYERS, LAYER, BS = 2, 1, 16
 
 
 # ---- the launcher, restated ---------------------------------------------------------------------
-def _chunk_mfma_heads(codec, dtype, d, heads, kvh):
+def _chunk_mfma_heads(codec, dtype, d, heads, kvh, buf=True):
     group = heads // kvh
     h84 = codec == "hamming84" and d in (32, 64, 128)
     golay = codec != "hamming84" and d == 128
-    if not (h84 or golay) or dtype != F16:
+    if not (h84 or golay) or dtype != F16 or not buf:
         return 0
     if group == 1:
         return 1
     return next((g for g in (16, 8, 4, 2) if group % g == 0), 0)
 
 
-def _chunk_select(codec, dtype, d, heads, kvh):
+def _chunk_select(codec, dtype, d, heads, kvh, buf=True):
     """-> (kernel name, heads per column group or per workgroup, workgroups per CU) at q_len > 1
-    for a query with 16-byte aligned rows."""
-    gm = _chunk_mfma_heads(codec, dtype, d, heads, kvh)
+    for a query with 16-byte aligned rows; buf False: over a cache of 4 GiB or more (_select)."""
+    gm = _chunk_mfma_heads(codec, dtype, d, heads, kvh, buf)
     if gm:
         if codec == "hamming84":
             return f"paged_attn_h84_mfma_chunk_kernel<{d}>", gm, 4
         return f"paged_attn_golay_mfma_chunk_kernel<{'true' if codec == 'golay_packed' else 'false'}>", gm, 2
-    name, gq, per_cu = _select(codec, dtype, d, heads, kvh)  # the split kernels over the virtual batch
+    name, gq, per_cu = _select(codec, dtype, d, heads, kvh, buf)  # the split kernels over the virtual batch
     assert "split_kernel" in name
     return name, gq, per_cu
 

@@ -12,7 +12,8 @@ profiles/attention_paths/kernels.txt is a kernel trace of this file (the suite
 does not read it).
 
 Not reachable at a small shape, and not listed:
-- the 64-bit-addressed kernels (BUF = false): caches of 4 GiB and more only;
+- the 64-bit-addressed kernels (BUF = false): caches of 4 GiB and more only
+  (`_select(..., buf=False)` restates their choice; tests/test_paged_cache_large.py runs them);
 - Hamming(8,4) VEC 4 at W 32 / 64 and Golay at W 64: compiled, but head_dim
   would exceed 256, which kvecc_paged_attention refuses.
 Reachable only at other shapes than the usual ones: with fp16 queries every
@@ -67,41 +68,44 @@ def _words(codec, d):
     return d // 4 if codec == "hamming84" else (d + 2) // 3
 
 
-def _mfma_heads(codec, dtype, d, heads, kvh):
+def _mfma_heads(codec, dtype, d, heads, kvh, buf=True):
     group = heads // kvh
     h84 = codec == "hamming84" and d in (32, 64, 128)
     golay = codec != "hamming84" and d == 128
-    if not (h84 or golay) or dtype != F16:
+    if not (h84 or golay) or dtype != F16 or not buf:
         return 0
     if group == 1:
         return 1 if h84 else 0
     return next((g for g in (16, 8, 4, 2) if group % g == 0), 0)
 
 
-def _heads_per_wg(codec, d, heads, kvh):
+def _heads_per_wg(codec, d, heads, kvh, buf=True):
     group = heads // kvh
     vec = (2 if d % 8 == 0 else 1) if codec == "hamming84" else 3
     w = _pow2(_cdiv(_words(codec, d), vec))
-    if w < 8 or w > 32 or (codec == "hamming84" and d % 8 != 0):
+    if not buf or w < 8 or w > 32 or (codec == "hamming84" and d % 8 != 0):
         return 1
     gmax = 2 if codec == "golay_packed" else 4
     return 4 if group % 4 == 0 and gmax >= 4 else 2 if group % 2 == 0 else 1
 
 
-def _select(codec, dtype, d, heads, kvh):
-    """-> (kernel name, query heads per workgroup, workgroups per CU of its split choice)."""
-    gm = _mfma_heads(codec, dtype, d, heads, kvh)
+def _select(codec, dtype, d, heads, kvh, buf=True):
+    """-> (kernel name, query heads per workgroup, workgroups per CU of its split choice).
+    buf: the caches are buffer-addressable (attn_setup's `fits`: under 4 GiB); False restates the
+    launcher's choice for a cache of 4 GiB or more -- no matrix cores, one head per workgroup."""
+    gm = _mfma_heads(codec, dtype, d, heads, kvh, buf)
     if gm:
         if codec == "hamming84":
             return f"paged_attn_h84_mfma_kernel<{d}, {gm}>", gm, 4
         return f"paged_attn_golay_mfma_kernel<{gm}, {'true' if codec == 'golay_packed' else 'false'}>", gm, 2
-    gq = _heads_per_wg(codec, d, heads, kvh)
+    gq = _heads_per_wg(codec, d, heads, kvh, buf)
     if codec == "hamming84":
         vec = 2 if gq > 1 else 4 if d % 16 == 0 else 1
     else:
         vec = 3
     w = _pow2(_cdiv(_words(codec, d), vec))
-    return f"paged_attn_split_kernel<{_TNAME[dtype]}, {_CODEC[codec]}, {vec}, {w}, true, {gq}, 0, 0>", gq, 4
+    b = "true" if buf else "false"
+    return f"paged_attn_split_kernel<{_TNAME[dtype]}, {_CODEC[codec]}, {vec}, {w}, {b}, {gq}, 0, 0>", gq, 4
 
 
 def _choose_split(bh, mcl, per_cu=4):
