@@ -57,8 +57,23 @@ enum { KVECC_CODEC_NONE = 0, KVECC_CODEC_H74 = 1, KVECC_CODEC_H84 = 2, KVECC_COD
         * Golay(24,12) codewords stored as 3 little-endian bytes, a token row of
         * g = ceil(d/3) codewords padded to KVECC_GOLAY_PACKED_ROW(g) bytes --
         * 132 B instead of the reference's 172 B (int32) at d = 128 */
-       KVECC_CODEC_GOLAY_PACKED = 4 };
+       KVECC_CODEC_GOLAY_PACKED = 4,
+       /* append-mode caches only (kvecc_shim_append[_ragged], kvecc_paged_attention,
+        * kvecc_paged_attention_chunk[_ragged] and their cpu twins; not a reference layout):
+        * KVECC_CODEC_NONE's nibbles two per byte.  head_dim % 8 == 0 and head_dim <= 256
+        * (anything else is KVECC_EINVAL before any launch); a token row is
+        * KVECC_INT4_PACKED_ROW(d) = d / 2 bytes, byte i holding value 2i in bits 0-3 and
+        * value 2i + 1 in bits 4-7; the nibbles are exactly those KVECC_CODEC_NONE stores
+        * (same quantiser, same scale rules, same + 8 offset) and the fp32 scales are that
+        * cache's bit for bit.  Cache tensor: uint8 [blocks, num_layers, kv_heads,
+        * block_size * head_dim / 2].  There is no code to exercise, so inject != 0 is
+        * KVECC_EINVAL; caches of 4 GiB and more are KVECC_EINVAL (no 64-bit-addressed
+        * kernels); and every other entry refuses the codec with KVECC_EINVAL: the windowed,
+        * interpolating, counted and repairing attention entries, kvecc_cache_scrub (nothing
+        * to scrub), kvecc_shim_write and kvecc_shim_read[_batch] (overwrite mode). */
+       KVECC_CODEC_INT4_PACKED = 5 };
 #define KVECC_GOLAY_PACKED_ROW(g) ((3 * (g) + 3) / 4 * 4)
+#define KVECC_INT4_PACKED_ROW(d) ((d) / 2)
 
 /* Row scale rule of the INT4 quantizer.  The reference computes
  * `abs_max / 7.0` with a Python-scalar divisor (paged_cache_ecc.py:330); torch
@@ -337,7 +352,11 @@ KVECC_API int kvecc_shim_write_strided(const void *k, const void *v, int64_t k_b
  * of an append at start_pos 0 holds the bits kvecc_shim_write stores for a
  * batch of b + 1.  Same dtypes, codecs, scale_rule and n_bits clamps as
  * kvecc_shim_write; d <= 512; table_stride >= 1; batch == 0 or q_len == 0
- * enqueues nothing. */
+ * enqueues nothing.
+ * kvecc_shim_append and kvecc_shim_append_ragged (and their cpu twins) also take
+ * KVECC_CODEC_INT4_PACKED: KVECC_CODEC_NONE's nibbles and scales, the row stored
+ * as d / 2 bytes, byte i = value 2i | value (2i + 1) << 4.  d % 8 == 0 and
+ * d <= 256, inject == 0; anything else is KVECC_EINVAL before any launch. */
 KVECC_API int kvecc_shim_append(const void *k, const void *v, int64_t k_batch_stride,
                                 int64_t k_seq_stride, int64_t k_head_stride,
                                 int64_t v_batch_stride, int64_t v_seq_stride,
@@ -458,7 +477,23 @@ KVECC_API int kvecc_shim_read_batch(const void *k_cache, const void *v_cache, co
  * A deliberate difference: kvecc_shim_read dequantizes a NONE byte raw (all 8
  * bits, unmasked), the attention kernels read its low nibble.  The two agree on
  * every byte the write, the 4-bit injection and a 4-bit ageing can produce
- * (b < 16) and differ only on bytes nothing in the library stores. */
+ * (b < 16) and differ only on bytes nothing in the library stores.
+ *
+ * Packed INT4 caches (KVECC_CODEC_INT4_PACKED; no reference counterpart).  The
+ * same three entries and their twins take the unprotected baseline two nibbles
+ * per byte: uint8 [blocks, num_layers, kv_heads, block_size * head_dim / 2], a
+ * token row of head_dim / 2 bytes, byte i holding value 2i in bits 0-3 and value
+ * 2i + 1 in bits 4-7, each worth (nibble - 8) * scale; scales as for every other
+ * codec.  head_dim % 8 == 0 and head_dim <= 256.  The query dtypes, the GQA map,
+ * -1 blocks, the max_context_len clamp, the workspace functions and the empty
+ * value (-8.0) are the byte caches'; a packed cache returns the bits the
+ * KVECC_CODEC_NONE cache of the same nibbles returns wherever both take the same
+ * kernels' geometry.  Caches of 4 GiB and more (cache bytes or scale bytes past
+ * 32 bits) are KVECC_EINVAL: the family has buffer-addressed kernels only.  Rows
+ * the call does not name -- past a sequence's length, in blocks no table entry
+ * names, of other layers -- are never given weight, whatever their bytes and
+ * scales (NaN included).  kvecc_paged_attention_window, _interp, _stats, _repair
+ * and _golay_stats refuse the codec with KVECC_EINVAL. */
 KVECC_API int64_t kvecc_paged_attention_workspace(int64_t batch, int64_t heads, int64_t head_dim,
                                                   int64_t max_context_len);
 KVECC_API int kvecc_paged_attention(const void *query, int q_dtype, const void *k_cache,
@@ -573,7 +608,8 @@ KVECC_API int kvecc_paged_attention_interp(const void *query, int64_t q_batch_st
  * the GQA map, the spans and the max_context_len clamp are
  * kvecc_paged_attention_chunk_ragged's, except that q_spans may be NULL (the
  * uniform call: first 0, count q_max) and q_max 1 is allowed and is the decode
- * step.  codec: KVECC_CODEC_H84, _H74, _NONE, _GOLAY or _GOLAY_PACKED; query
+ * step.  codec: KVECC_CODEC_H84, _H74, _NONE, _GOLAY or _GOLAY_PACKED (KVECC_CODEC_INT4_PACKED is
+ * KVECC_EINVAL whatever the window: the plain entries serve that layout); query
  * dtypes fp32, fp16, bf16.  Plain attention only: no interpolation, no
  * statistics, no repair.
  *

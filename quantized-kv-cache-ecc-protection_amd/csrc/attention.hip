@@ -228,6 +228,21 @@ template <typename A>
 constexpr bool is_byte = std::is_same<A, ByteAttnArgs>::value || std::is_same<A, ByteChunkArgs>::value ||
                          std::is_same<A, ByteUniformArgs>::value;
 
+// Packed INT4 caches (KVECC_CODEC_INT4_PACKED, kvecc.h: KVECC_CODEC_NONE's nibbles two per byte,
+// rows of head_dim / 2 bytes) run a family of kernels of their own names over argument blocks of
+// their own types: every other kernel keeps its block, its text and its registers.  The blocks add
+// nothing -- AttnArgs::rowb carries the row's bytes, as for packed Golay -- and mirror the byte
+// family's three: the decode entry's, the ragged one, and the uniform matrix-core chunk kernels'
+// narrower one (see RaggedArgs).  The family needs no decode table: the general path unpacks in
+// Chunk::decode, the matrix-core kernels have a body of their own (attn_i4p_mfma_body.inc).
+// Buffer-addressed caches only: 4 GiB and more is KVECC_EINVAL.
+struct PackedAttnArgs : AttnArgs {};
+struct PackedChunkArgs : RaggedArgs {};
+struct PackedUniformArgs : ChunkArgs {};
+template <typename A>
+constexpr bool is_packed_int4 = std::is_same<A, PackedAttnArgs>::value || std::is_same<A, PackedChunkArgs>::value ||
+                                std::is_same<A, PackedUniformArgs>::value;
+
 // Windowed calls (kvecc_paged_attention_window, kvecc.h "Windowed attention") run
 // kernels of their own names over an argument block of their own type: every other
 // kernel keeps its block, its text and its registers.  A query row at position p
@@ -331,12 +346,15 @@ __device__ __forceinline__ uint32_t h84_interp_fix4(uint32_t w, uint32_t wl, uin
   return h84_encode4(interp_word(q, ql, qr, ty));
 }
 
+template <int NB>
+__device__ __forceinline__ void load_chunk(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t *w);  // (below)
+
 // Lane chunk c of a token row: VEC 32-bit words = 4*VEC H(8,4) codewords, or
 // VEC Golay codewords (3*VEC values; codewords past the row's last are read
 // clamped and contribute nothing, their values fall outside [0, d)); E values.
 template <int CODEC, int VEC>
 struct Chunk {
-  static constexpr int E = CODEC == KVECC_CODEC_H84 ? 4 * VEC : 3 * VEC;
+  static constexpr int E = CODEC == KVECC_CODEC_INT4_PACKED ? 8 * VEC : CODEC == KVECC_CODEC_H84 ? 4 * VEC : 3 * VEC;
   // decode() returns (n - 8) + kOffset: the Golay path skips the subtraction
   // per element and the kernel folds -8 * kOffset into the sums instead
   static constexpr float kOffset = is_golay(CODEC) ? 8.0f : 0.0f;
@@ -345,7 +363,11 @@ struct Chunk {
   uint32_t w[VEC];
   __device__ __forceinline__ void load_buf(const AttnArgs &a, __amdgpu_buffer_rsrc_t rs, int32_t row,
                                            int c) {
-    if constexpr (CODEC == KVECC_CODEC_H84) {
+    if constexpr (CODEC == KVECC_CODEC_INT4_PACKED) {
+      // packed INT4 (kvecc.h): VEC dwords = 8 VEC values of a row of d / 2 bytes, one load
+      static_assert(CODEC != KVECC_CODEC_INT4_PACKED || VEC == 1 || VEC == 2, "packed INT4 lanes own 8 or 16 values");
+      load_chunk<4 * VEC>(rs, (uint32_t)row * a.rowb + 4u * VEC * c, w);
+    } else if constexpr (CODEC == KVECC_CODEC_H84) {
       const uint32_t off = (uint32_t)row * (uint32_t)a.d + 4u * VEC * c;
       if constexpr (VEC % 4 == 0) {
 #pragma unroll
@@ -391,7 +413,11 @@ struct Chunk {
     }
   }
   __device__ __forceinline__ void load(const AttnArgs &a, const void *cache, int64_t row, int c) {
-    if constexpr (CODEC == KVECC_CODEC_H84) {
+    if constexpr (CODEC == KVECC_CODEC_INT4_PACKED) {  // (no kernel takes it: this family is buffer-addressed only)
+      const uint32_t *p = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(cache) + row * a.rowb);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) w[k] = p[VEC * c + k];
+    } else if constexpr (CODEC == KVECC_CODEC_H84) {
       const uint8_t *p = reinterpret_cast<const uint8_t *>(cache) + row * a.d + 4 * VEC * c;
       if constexpr (VEC % 4 == 0) {
 #pragma unroll
@@ -454,7 +480,19 @@ struct Chunk {
   template <int DEC = 0>
   __device__ __forceinline__ void decode(const h84_lut_t *lut, const uint32_t *gtab, float *v) const {
     constexpr bool SP = (DEC & 1) != 0;
-    if constexpr (CODEC == KVECC_CODEC_H84) {
+    if constexpr (CODEC == KVECC_CODEC_INT4_PACKED) {
+      // no table: the even and the odd nibbles of a word, one per byte (a mask; a shift and a
+      // mask), then one v_cvt_f32_ubyteN and the - 8 per value -- value 2i is byte i's low nibble
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const uint32_t ev = w[k] & 0x0F0F0F0Fu, od = (w[k] >> 4) & 0x0F0F0F0Fu;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          v[8 * k + 2 * i] = (float)((ev >> (8 * i)) & 0xFFu) - 8.0f;
+          v[8 * k + 2 * i + 1] = (float)((od >> (8 * i)) & 0xFFu) - 8.0f;
+        }
+      }
+    } else if constexpr (CODEC == KVECC_CODEC_H84) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
 #pragma unroll
@@ -814,6 +852,29 @@ __global__ __launch_bounds__(kBlock) void paged_attn_split_byte_chunk_kernel(Byt
 #include "attn_split_body.inc"
 #undef ATTN_BODY_CHUNK
 }
+// the packed INT4 family's general path (KVECC_CODEC_INT4_PACKED): the same body with the packed row
+// loader (Chunk<KVECC_CODEC_INT4_PACKED, VEC>: VEC dwords = 8 VEC values per lane) and the [packed]
+// island, buffer-addressed caches only
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_i4p_kernel(PackedAttnArgs a) {
+  constexpr int CODEC = KVECC_CODEC_INT4_PACKED, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 0
+#define ATTN_BODY_PACKED 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_PACKED
+#undef ATTN_BODY_CHUNK
+}
+template <typename T, int VEC, int W, int G = 1>
+__global__ __launch_bounds__(kBlock) void paged_attn_split_i4p_chunk_kernel(PackedChunkArgs a) {
+  constexpr int CODEC = KVECC_CODEC_INT4_PACKED, UR = 0, DEC = 0;
+  constexpr bool BUF = true;
+#define ATTN_BODY_CHUNK 1
+#define ATTN_BODY_PACKED 1
+#include "attn_split_body.inc"
+#undef ATTN_BODY_PACKED
+#undef ATTN_BODY_CHUNK
+}
 // the windowed entry's kernels (kvecc_paged_attention_window): the chunk form with the [window]
 // islands, every codec and query dtype; Hamming(8,4)'s instantiations serve the byte family too
 // (WindowArgs::tab)
@@ -1139,6 +1200,32 @@ __global__ __launch_bounds__(kBlock, 2) void paged_attn_h84_mfma_window_kernel(W
 #undef ATTN_BODY_CHUNK
 }
 
+// the packed INT4 family's (KVECC_CODEC_INT4_PACKED): the decode, chunk and ragged kernels over a body
+// of their own, attn_i4p_mfma_body.inc -- Hamming(8,4)'s operand maps over half the bytes, nibbles
+// unpacked in registers, no decode table in LDS.  head_dim 64 and 128.
+template <int D, int G>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_i4p_mfma_kernel(PackedAttnArgs a) {
+#define ATTN_BODY_CHUNK 0
+#include "attn_i4p_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_i4p_mfma_chunk_kernel(PackedUniformArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<ChunkArgs>;
+#define ATTN_BODY_CHUNK 1
+#include "attn_i4p_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+template <int D>
+__global__ __launch_bounds__(kBlock, 2) void paged_attn_i4p_mfma_ragged_kernel(PackedChunkArgs a) {
+  constexpr int G = 16;
+  using ChunkMap = ChunkMapT<RaggedArgs>;
+#define ATTN_BODY_CHUNK 1
+#include "attn_i4p_mfma_body.inc"
+#undef ATTN_BODY_CHUNK
+}
+
 // ---- GQA on the matrix cores, Golay(24,12) int32 caches, head_dim 128 ---------
 //
 // The H(8,4) kernel's scheme with codeword-aligned operand maps (a row is 43
@@ -1267,15 +1354,19 @@ constexpr bool takes_golay = std::is_same<A, AttnArgs>::value || std::is_same<A,
                              std::is_same<A, WindowArgs>::value;
 // The blocks whose kernels address the caches through buffer descriptors only (caches under 4 GiB)
 template <typename A>
-constexpr bool buf_only = is_interp<A> || is_stats<A> || is_repair<A>;
+constexpr bool buf_only = is_interp<A> || is_stats<A> || is_repair<A> || is_packed_int4<A>;
 
 // f(int_tag<CODEC>) for the codec of block A's kernels (the byte family arrives as Hamming(8,4))
 template <typename A, typename F>
 static int with_codec(const char *entry, int codec, F &&f) {
-  if (codec == KVECC_CODEC_H84) return f(int_tag<KVECC_CODEC_H84>{});
-  if constexpr (takes_golay<A>) {
-    if (codec == KVECC_CODEC_GOLAY) return f(int_tag<KVECC_CODEC_GOLAY>{});
-    if (codec == KVECC_CODEC_GOLAY_PACKED) return f(int_tag<KVECC_CODEC_GOLAY_PACKED>{});
+  if constexpr (is_packed_int4<A>) {  // the family's blocks take its one codec
+    if (codec == KVECC_CODEC_INT4_PACKED) return f(int_tag<KVECC_CODEC_INT4_PACKED>{});
+  } else {
+    if (codec == KVECC_CODEC_H84) return f(int_tag<KVECC_CODEC_H84>{});
+    if constexpr (takes_golay<A>) {
+      if (codec == KVECC_CODEC_GOLAY) return f(int_tag<KVECC_CODEC_GOLAY>{});
+      if (codec == KVECC_CODEC_GOLAY_PACKED) return f(int_tag<KVECC_CODEC_GOLAY_PACKED>{});
+    }
   }
   return set_error(KVECC_EINVAL, "%s: no kernel of this call's mode decodes codec %d", entry, codec);
 }
@@ -1290,6 +1381,12 @@ constexpr auto split_kernel() {
     return &paged_attn_split_chunk_kernel<T, CODEC, VEC, W, BUF, G>;
   } else if constexpr (std::is_same<A, WindowArgs>::value) {
     return &paged_attn_split_window_kernel<T, CODEC, VEC, W, BUF, G>;
+  } else if constexpr (is_packed_int4<A>) {
+    static_assert(CODEC == KVECC_CODEC_INT4_PACKED && BUF, "the packed INT4 kernels: their codec, buffer-addressed");
+    if constexpr (std::is_same<A, PackedAttnArgs>::value)
+      return &paged_attn_split_i4p_kernel<T, VEC, W, G>;
+    else
+      return &paged_attn_split_i4p_chunk_kernel<T, VEC, W, G>;
   } else if constexpr (std::is_same<A, StatsArgs>::value && is_golay(CODEC)) {
     static_assert(BUF, "the counted kernels are buffer-addressed");
     return &paged_attn_split_golay_stats_kernel<T, CODEC, VEC, W, G>;
@@ -1353,6 +1450,8 @@ static int launch_split(const char *entry, const A &a, dim3 grid, hipStream_t st
 // rows and accumulators per lane, 4 words took 188 VGPRs at G = 4)
 constexpr int kH84GqaVec = 2;
 static int attn_vec(int codec, int64_t d, bool gqa = false) {
+  // packed INT4: 2 dwords = 16 values per lane, Hamming(8,4)'s count; 1 = 8 under GQA or at head_dim % 16 != 0
+  if (codec == KVECC_CODEC_INT4_PACKED) return !gqa && d % 16 == 0 ? 2 : 1;
   if (codec == KVECC_CODEC_H84)
     return gqa && d % 8 == 0 ? kH84GqaVec : d % (4 * kH84Vec) == 0 ? kH84Vec : d % 16 == 0 ? 4 : 1;
   return codec == KVECC_CODEC_GOLAY ? kGolayVec : kGolayPackedVec;
@@ -1385,7 +1484,7 @@ template <typename T, int CODEC, int VEC, typename A>
 static int launch_split_g(const char *entry, const A &a, int64_t batch, int gq, hipStream_t st) {
   dim3 grid((unsigned)a.nsplit, (unsigned)(batch * a.heads / gq));
   if (gq == 1) return launch_split<T, CODEC, VEC>(entry, a, grid, st);
-  constexpr int GV = CODEC == KVECC_CODEC_H84 ? kH84GqaVec : VEC;
+  constexpr int GV = CODEC == KVECC_CODEC_H84 ? kH84GqaVec : CODEC == KVECC_CODEC_INT4_PACKED ? 1 : VEC;
   if constexpr (CODEC != KVECC_CODEC_GOLAY_PACKED)
     if (gq == 4) return launch_split_gqa<T, CODEC, GV, 4>(a, grid, st);
   return launch_split_gqa<T, CODEC, GV, 2>(a, grid, st);
@@ -1401,6 +1500,11 @@ static int launch_attn(const char *entry, const A &a, int64_t batch, int gq, hip
       rc = launch_split_g<T, CODEC, kH84Vec>(entry, a, batch, gq, st);  // 16-byte loads, 16 codewords per lane
     else if (a.d % 16 == 0)
       rc = launch_split_g<T, CODEC, 4>(entry, a, batch, gq, st);
+    else
+      rc = launch_split_g<T, CODEC, 1>(entry, a, batch, gq, st);
+  } else if constexpr (CODEC == KVECC_CODEC_INT4_PACKED) {
+    if (a.d % 16 == 0)
+      rc = launch_split_g<T, CODEC, 2>(entry, a, batch, gq, st);  // 8-byte loads, 16 values per lane (attn_vec)
     else
       rc = launch_split_g<T, CODEC, 1>(entry, a, batch, gq, st);
   } else if constexpr (CODEC == KVECC_CODEC_GOLAY) {
@@ -1441,6 +1545,8 @@ constexpr auto decode_mfma_kernel() {
   if constexpr (std::is_same<A, ByteAttnArgs>::value) {
     static_assert(CODEC == KVECC_CODEC_H84, "the byte family decodes Hamming(8,4)'s layout");
     return &paged_attn_byte_mfma_kernel<D, G>;
+  } else if constexpr (std::is_same<A, PackedAttnArgs>::value) {
+    return &paged_attn_i4p_mfma_kernel<D, G>;
   } else {
     static_assert(std::is_same<A, AttnArgs>::value, "no decode matrix-core kernel takes this block");
     if constexpr (is_golay(CODEC))
@@ -1457,6 +1563,8 @@ static int launch_decode_mfma(const char *entry, int codec, const A &a, int64_t 
     constexpr int CODEC = decltype(c)::value, G = decltype(g)::value;
     if constexpr (is_golay(CODEC) && G == 1) {  // Golay MHA stays on the split kernels (attn_mfma_heads)
       return set_error(KVECC_EINVAL, "%s: no Golay matrix-core kernel for one query head per workgroup", entry);
+    } else if constexpr (is_packed_int4<A> && decltype(d)::value == 32) {  // head_dim 64 and 128 (attn_mfma_heads)
+      return set_error(KVECC_EINVAL, "%s: no packed INT4 matrix-core kernel at head_dim 32", entry);
     } else {
       KVECC_LAUNCH((decode_mfma_kernel<A, CODEC, decltype(d)::value, G>()), grid, dim3(kBlock), 0, st, a);
       return (int)KVECC_OK;
@@ -1490,7 +1598,8 @@ static int attn_mfma_heads(int codec, int q_dtype, const void *query, int64_t d,
   const bool h84 = codec == KVECC_CODEC_H84 && (d == 32 || d == 64 || d == 128);
   const bool golay = (codec == KVECC_CODEC_GOLAY || codec == KVECC_CODEC_GOLAY_PACKED) &&
                      d == 128;
-  if (!(h84 || golay) || q_dtype != KVECC_F16 || !buf || !aligned(query, 16)) return 0;
+  const bool i4p = codec == KVECC_CODEC_INT4_PACKED && (d == 64 || d == 128);  // Hamming(8,4)'s groups, MHA included
+  if (!(h84 || golay || i4p) || q_dtype != KVECC_F16 || !buf || !aligned(query, 16)) return 0;
   // MHA (one query head per cache head): H(8,4) too, one of the 16 MFMA
   // columns used -- the matrix cores take the dot products and the V update
   // off the VALU, and the table lookups are the only per-value LDS work:
@@ -1498,7 +1607,7 @@ static int attn_mfma_heads(int codec, int q_dtype, const void *query, int64_t d,
   // Golay MHA stays on the VALU kernels (packed 76 vs 68 us, int32 86 vs 73:
   // its per-codeword decode, not the arithmetic, is the work).
   // (tools/exp/run_attn_exp.py, profiles/r04/attn/mfma_mha_ab.log)
-  if (group == 1) return h84 ? 1 : 0;
+  if (group == 1) return h84 || i4p ? 1 : 0;
   return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
 }
 
@@ -1511,7 +1620,8 @@ static int attn_chunk_mfma_heads(int codec, int q_dtype, const void *query, int6
   const int64_t group = heads / kv_heads;
   const bool h84 = codec == KVECC_CODEC_H84 && (d == 32 || d == 64 || d == 128);
   const bool golay = (codec == KVECC_CODEC_GOLAY || codec == KVECC_CODEC_GOLAY_PACKED) && d == 128;
-  if (!(h84 || golay) || q_dtype != KVECC_F16 || !buf) return 0;
+  const bool i4p = codec == KVECC_CODEC_INT4_PACKED && (d == 64 || d == 128);
+  if (!(h84 || golay || i4p) || q_dtype != KVECC_F16 || !buf) return 0;
   if (!aligned(query, 16) || sb % 8 || st % 8 || sh % 8) return 0;
   if (group == 1) return 1;
   return group % 16 == 0 ? 16 : group % 8 == 0 ? 8 : group % 4 == 0 ? 4 : group % 2 == 0 ? 2 : 0;
@@ -1522,7 +1632,14 @@ static int attn_chunk_mfma_heads(int codec, int q_dtype, const void *query, int6
 // blocks ChunkArgs / ByteUniformArgs (see RaggedArgs, ByteUniformArgs).
 template <typename A, int CODEC, int D>
 constexpr auto tile_kernel() {
-  if constexpr (is_golay(CODEC)) {
+  if constexpr (is_packed_int4<A>) {
+    if constexpr (std::is_same<A, PackedUniformArgs>::value) {
+      return &paged_attn_i4p_mfma_chunk_kernel<D>;
+    } else {
+      static_assert(std::is_same<A, PackedChunkArgs>::value, "no packed INT4 tile kernel takes this block");
+      return &paged_attn_i4p_mfma_ragged_kernel<D>;
+    }
+  } else if constexpr (is_golay(CODEC)) {
     constexpr bool PACKED = CODEC == KVECC_CODEC_GOLAY_PACKED;
     if constexpr (std::is_same<A, ChunkArgs>::value) {
       return &paged_attn_golay_mfma_chunk_kernel<PACKED>;
@@ -1572,12 +1689,22 @@ static int launch_tiles(const char *entry, int codec, const A &a, int64_t batch,
       u.tab = a.tab;
       return launch_tiles(entry, codec, u, batch, tiles, st);
     }
+  } else if constexpr (std::is_same<A, PackedChunkArgs>::value) {
+    if (!a.q_spans) {
+      PackedUniformArgs u;
+      static_cast<ChunkArgs &>(u) = a;
+      return launch_tiles(entry, codec, u, batch, tiles, st);
+    }
   }
   const dim3 grid((unsigned)(a.nsplit * tiles), (unsigned)(batch * (a.heads >> a.cg_log2)));
   const int rc = with_codec<A>(entry, codec, [&](auto c) {
     return with_head_dim(a.d, [&](auto d) {
-      KVECC_LAUNCH((tile_kernel<A, decltype(c)::value, decltype(d)::value>()), grid, dim3(kBlock), 0, st, a);
-      return (int)KVECC_OK;
+      if constexpr (is_packed_int4<A> && decltype(d)::value == 32) {  // head_dim 64 and 128 (attn_chunk_mfma_heads)
+        return set_error(KVECC_EINVAL, "%s: no packed INT4 matrix-core kernel at head_dim 32", entry);
+      } else {
+        KVECC_LAUNCH((tile_kernel<A, decltype(c)::value, decltype(d)::value>()), grid, dim3(kBlock), 0, st, a);
+        return (int)KVECC_OK;
+      }
     });
   });
   if (rc != KVECC_OK) return rc;
@@ -1631,9 +1758,13 @@ static int attn_setup(const char *entry, const AttnCall &c, int &codec, A &a, At
   if (c.head_dim < 1 || c.head_dim > kAttnMaxD)
     return set_error(KVECC_EINVAL, "%s: head_dim %lld not in [1, %d]", entry, (long long)c.head_dim, kAttnMaxD);
   if (codec != KVECC_CODEC_NONE && codec != KVECC_CODEC_H74 && codec != KVECC_CODEC_H84 &&
-      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED)
-    return set_error(KVECC_EINVAL, "%s: codec %d (int4, hamming74, hamming84, golay or golay_packed only)", entry,
+      codec != KVECC_CODEC_GOLAY && codec != KVECC_CODEC_GOLAY_PACKED && codec != KVECC_CODEC_INT4_PACKED)
+    return set_error(KVECC_EINVAL,
+                     "%s: codec %d (int4, hamming74, hamming84, golay or golay_packed, or int4_packed, only)", entry,
                      codec);
+  const bool i4p = codec == KVECC_CODEC_INT4_PACKED;  // kvecc.h: whole dwords per row
+  if (i4p && c.head_dim % 8 != 0)
+    return set_error(KVECC_EINVAL, "%s: int4_packed head_dim must be a multiple of 8", entry);
   // the byte family (kvecc.h): Hamming(8,4)'s layout, rules and launch geometry, its own kernels
   const int table = codec;
   if (codec == KVECC_CODEC_NONE || codec == KVECC_CODEC_H74) codec = KVECC_CODEC_H84;
@@ -1677,15 +1808,15 @@ static int attn_setup(const char *entry, const AttnCall &c, int &codec, A &a, At
   a.heads = c.heads;
   a.kv_heads = c.kv_heads;
   a.d = c.head_dim;
-  a.g = codec == KVECC_CODEC_H84 ? c.head_dim / 4 : (c.head_dim + 2) / 3;
-  a.rowb = (uint32_t)KVECC_GOLAY_PACKED_ROW(a.g);
+  a.g = i4p ? c.head_dim / 8 : codec == KVECC_CODEC_H84 ? c.head_dim / 4 : (c.head_dim + 2) / 3;  // (i4p: dwords)
+  a.rowb = (uint32_t)(i4p ? KVECC_INT4_PACKED_ROW(c.head_dim) : KVECC_GOLAY_PACKED_ROW(a.g));
   a.layers = c.num_layers;
   a.layer = c.layer;
   a.bs = c.block_size;
   a.max_blocks = c.max_blocks;
   a.ctx_cap = std::min(max_context_len, c.max_blocks * c.block_size);
   a.sm_scale = c.sm_scale;
-  a.empty_value = codec == KVECC_CODEC_H84 ? -8.0f : 0.0f;
+  a.empty_value = is_golay(codec) ? 0.0f : -8.0f;
   if constexpr (is_chunk<A>) {
     a.q_len = (uint32_t)c.q_len;
     a.vb0 = 0;
@@ -1695,10 +1826,12 @@ static int attn_setup(const char *entry, const AttnCall &c, int &codec, A &a, At
     a.cg_log2 = 0;
     a.q_spans = c.q_spans;
   }
-  const int64_t cb = rows_total * (codec == KVECC_CODEC_H84            ? c.head_dim
-                                   : codec == KVECC_CODEC_GOLAY_PACKED ? (int64_t)a.rowb
-                                                                       : 4 * a.g);
+  const int64_t cb = rows_total * (codec == KVECC_CODEC_H84                    ? c.head_dim
+                                   : codec == KVECC_CODEC_GOLAY_PACKED || i4p ? (int64_t)a.rowb
+                                                                               : 4 * a.g);
   const bool fits = cb <= 0xFFFFFFFFLL && rows_total * 4 <= 0xFFFFFFFFLL;
+  if (i4p && !fits)
+    return set_error(KVECC_EINVAL, "%s: int4_packed caches of 4 GiB or more are not supported", entry);
   a.cache_bytes = fits ? (uint32_t)cb : 0u;  // 0 selects the 64-bit-addressed kernels
   a.scale_bytes = fits ? (uint32_t)(rows_total * 4) : 0u;
   const int rc = plan(a, fits, max_context_len, p);
@@ -1716,7 +1849,7 @@ static int attn_setup(const char *entry, const AttnCall &c, int &codec, A &a, At
     a.ctr = attn_counter_slot(c.stream);
     if (!a.ctr) return KVECC_EHIP;
   }
-  if (codec != KVECC_CODEC_H84) {
+  if (is_golay(codec)) {
     a.par = golay_parity_table_dev();
     a.cor = golay_correct_table_dev();
     a.atab = golay_attn_table_dev();
@@ -1740,7 +1873,7 @@ static int paged_attention_decode(const AttnCall &c) {
     p.gm = attn_mfma_heads(codec, c.q_dtype, c.query, c.head_dim, c.heads, c.kv_heads, fits);
     if (p.gm)  // kMfma*WgPerCu workgroups per CU, never finer than the workspace allows
       a.split = std::max(choose_split(c.batch * c.heads / p.gm, max_context_len,
-                                      codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu : kMfmaWgPerCu),
+                                      is_golay(codec) ? kMfmaGolayWgPerCu : kMfmaWgPerCu),
                          choose_split(std::max<int64_t>(1, c.batch * c.heads / 4), max_context_len));
     else
       a.split = choose_split(c.batch * c.heads / p.gq, max_context_len);
@@ -1766,7 +1899,14 @@ static int paged_attention_decode(const AttnCall &c) {
     });
   };
   const bool bytes = c.codec == KVECC_CODEC_NONE || c.codec == KVECC_CODEC_H74;
-  const int lrc = bytes ? run(a) : run(static_cast<const AttnArgs &>(a));
+  int lrc;
+  if (c.codec == KVECC_CODEC_INT4_PACKED) {  // the packed INT4 family's block
+    PackedAttnArgs pa;
+    static_cast<AttnArgs &>(pa) = a;
+    lrc = run(pa);
+  } else {
+    lrc = bytes ? run(a) : run(static_cast<const AttnArgs &>(a));
+  }
   if (lrc != KVECC_OK) return lrc;
   return check_launch("paged_attention");
 }
@@ -1797,6 +1937,8 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
     return set_error(KVECC_EINVAL, "paged_attention_stats: codec %d (the counted kernels need hamming84)", codec);
   if (m.interp && codec != KVECC_CODEC_H84)
     return set_error(KVECC_EINVAL, "paged_attention_interp: codec %d (interpolation needs hamming84)", codec);
+  if (windowed && codec == KVECC_CODEC_INT4_PACKED)
+    return set_error(KVECC_EINVAL, "paged_attention_window: no windowed kernel reads int4_packed caches");
   if (c.batch == 0 || c.q_len == 0 || c.heads == 0) return KVECC_OK;
   if (c.q_sb < 0 || c.q_st < 0 || c.q_sh < 0 || (c.heads > 1 && c.q_sh < c.head_dim) ||
       (c.q_len > 1 && c.q_st < c.head_dim))
@@ -1844,7 +1986,7 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
                                : choose_split(std::max<int64_t>(1, c.batch * c.heads / 4), max_context_len);
     a.split = std::max(choose_split(wgs, max_context_len,
                                     !p.gm                      ? 4
-                                    : codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu
+                                    : is_golay(codec)          ? kMfmaGolayWgPerCu
                                                                : kMfmaWgPerCu),
                        finest);
     // the counted combine as in the decode entry: one query head per workgroup of the split kernels
@@ -1868,7 +2010,7 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
     const int64_t rows = vbatch * c.heads, sinks = std::min<int64_t>(m.sinks, a.ctx_cap);
     const int64_t span = m.window + (p.gm ? 15 : 0);
     const int64_t wgs = p.gm ? c.batch * (c.heads / p.gm) * p.tiles : vbatch * c.heads / p.gq;
-    const int per_cu = !p.gm ? 4 : codec != KVECC_CODEC_H84 ? kMfmaGolayWgPerCu : kMfmaWgPerCu;
+    const int per_cu = !p.gm ? 4 : is_golay(codec) ? kMfmaGolayWgPerCu : kMfmaWgPerCu;
     for (int64_t split = choose_split(wgs, std::min<int64_t>(a.ctx_cap, sinks + span), per_cu);; split <<= 1) {
       const int64_t ss = cdiv(sinks, split), n = ss + cdiv(span + split - 1, split);
       if (n >= cdiv(a.ctx_cap, split)) break;
@@ -1905,7 +2047,12 @@ static int paged_attention_chunk_impl(const AttnCall &c, const AttnMode &m) {
     case AttnKind::repair: lrc = m.interp ? run(RepairInterpArgs{}) : run(RepairArgs{}); break;
     case AttnKind::counted: lrc = m.interp ? run(StatsInterpArgs{}) : run(StatsArgs{}); break;
     case AttnKind::windowed: lrc = run(WindowArgs{}); break;
-    default: lrc = m.interp ? run(InterpArgs{}) : bytes ? run(a) : run(RaggedArgs{}); break;
+    default:
+      lrc = m.interp                             ? run(InterpArgs{})
+            : bytes                              ? run(a)
+            : c.codec == KVECC_CODEC_INT4_PACKED ? run(PackedChunkArgs{})
+                                                 : run(RaggedArgs{});
+      break;
   }
   if (lrc != KVECC_OK) return lrc;
   return check_launch("paged_attention_chunk");
@@ -2003,6 +2150,8 @@ KVECC_API int kvecc_paged_attention_window(const void *query, int64_t q_batch_st
   if (window < 0 || sinks < 0)
     return set_error(KVECC_EINVAL, "paged_attention_window: negative window %lld or sinks %lld", (long long)window,
                      (long long)sinks);
+  if (codec == KVECC_CODEC_INT4_PACKED)  // whatever the window: the plain entries serve this layout
+    return set_error(KVECC_EINVAL, "paged_attention_window: no windowed kernel reads int4_packed caches");
   // No window, or one that covers every key a row can see (its key limit is at most ctx_cap =
   // min(max_context_len, max_blocks * block_size)): the plain entry, its kernels and its bits.
   const int64_t table_cap = max_blocks > 0 && block_size > 0 ? max_blocks * block_size : 0;

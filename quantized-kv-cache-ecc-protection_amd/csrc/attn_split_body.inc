@@ -16,6 +16,9 @@
 // The windowed kernels (paged_attn_split_window_kernel, `a` a WindowArgs, ATTN_BODY_CHUNK 1) define
 // ATTN_BODY_WINDOW: the [window] islands -- the row's lower key bound, the empty split's early exit, the
 // -1 rows between sinks and window; without it the preprocessed text is what it was.
+// The packed INT4 kernels (paged_attn_split_i4p*_kernel, `a` a PackedAttnArgs / PackedChunkArgs,
+// CODEC KVECC_CODEC_INT4_PACKED: Chunk's packed loader and table-free decode) define ATTN_BODY_PACKED: the
+// [packed] island, the windowed kernels' zero V scale for a -1 row; without it the text is what it was.
   constexpr bool SP = (DEC & 1) != 0;  // Chunk::decode's DEC bits (experiment forks only)
   using C = Chunk<CODEC, VEC>;
   constexpr int E = C::E;
@@ -271,8 +274,8 @@
       ks[u] = pks[u];
       vs[u] = pvs[u];
       ok[u] = pok[u];
-#ifdef ATTN_BODY_WINDOW  // [window] a -1 row stands in row 0 of the cache, which may be a released block's:
-      // its weight p = 0 must not meet a V scale that is no number (0 * NaN)
+#if defined(ATTN_BODY_WINDOW) || defined(ATTN_BODY_PACKED)  // [window] [packed] a -1 row stands in row 0 of the
+      // cache, which may be a released block's: its weight p = 0 must not meet a V scale that is no number (0 * NaN)
       if (!ok[u]) vs[u] = 0.0f;
 #endif
     }

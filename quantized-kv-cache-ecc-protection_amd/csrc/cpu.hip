@@ -624,8 +624,16 @@ struct HostShimRows {
            int n_bits_, int inject, float ber, int64_t seed0_, void *k_cache, void *v_cache, float *k_scales,
            float *v_scales, const int32_t *block_table, int64_t num_layers, int64_t block_size, int64_t layer) {
     if (d_ < 1) return set_error(KVECC_EINVAL, "%s: empty rows", fn);
-    if (codec_ < KVECC_CODEC_NONE || codec_ > KVECC_CODEC_GOLAY_PACKED)
+    // (packed INT4 is an append-mode layout: kvecc.h)
+    const bool append = std::strncmp(fn, "cpu_shim_append", 15) == 0;
+    if (codec_ < KVECC_CODEC_NONE || codec_ > (append ? KVECC_CODEC_INT4_PACKED : KVECC_CODEC_GOLAY_PACKED))
       return set_error(KVECC_EINVAL, "%s: bad codec %d", fn, codec_);
+    if (codec_ == KVECC_CODEC_INT4_PACKED) {
+      if (d_ % 8 != 0 || d_ > 256)
+        return set_error(KVECC_EINVAL, "%s: int4_packed head_dim %lld must be a multiple of 8 in [8, 256]", fn,
+                         (long long)d_);
+      if (inject) return set_error(KVECC_EINVAL, "%s: int4_packed has no code to inject errors into", fn);
+    }
     if (scale_rule_ != KVECC_SCALE_DIV7 && scale_rule_ != KVECC_SCALE_MUL_INV7)
       return set_error(KVECC_EINVAL, "%s: bad scale rule %d", fn, scale_rule_);
     if (x_dtype_ < KVECC_F32 || x_dtype_ > KVECC_BF16) return set_error(KVECC_EINVAL, "%s: bad dtype %d", fn, x_dtype_);
@@ -658,6 +666,13 @@ struct HostShimRows {
     for (int64_t j = 0; j < d; ++j) amax = std::max(amax, std::fabs(load_x(xs, x_dtype, r * d + j)));
     const float scale = row_scale(amax, scale_rule);
     scales[side][slot] = scale;
+    if (codec == KVECC_CODEC_INT4_PACKED) {  // KVECC_CODEC_NONE's nibbles, value 2i low and 2i + 1 high in byte i
+      uint8_t *c = reinterpret_cast<uint8_t *>(cache[side]) + slot * KVECC_INT4_PACKED_ROW(d);
+      for (int64_t j = 0; j < d; j += 2)
+        c[j / 2] = (uint8_t)(quantize_nibble(load_x(xs, x_dtype, r * d + j), scale) |
+                             quantize_nibble(load_x(xs, x_dtype, r * d + j + 1), scale) << 4);
+      return;
+    }
     if (!golay) {
       uint8_t *c = reinterpret_cast<uint8_t *>(cache[side]) + slot * g;
       for (int64_t j = 0; j < d; ++j) {
@@ -1071,6 +1086,11 @@ void attention_rows(const AttnCall &c, int threads, int64_t window = 0, int64_t 
             kv[3 * k + u] = ((float)(dw >> (4 * u) & 0xFu) - 8.0f) * s;
         }
       } else {
+        if (codec == KVECC_CODEC_INT4_PACKED) {  // two nibbles per byte, value 2i in bits 0-3 of byte i
+          const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * KVECC_INT4_PACKED_ROW(head_dim);
+          for (int64_t j = 0; j < head_dim; ++j) kv[j] = ((float)(c[j / 2] >> (4 * (j & 1)) & 0xFu) - 8.0f) * s;
+          return;
+        }
         const uint8_t *c = reinterpret_cast<const uint8_t *>(cache) + srow * head_dim;
         for (int64_t j = 0; j < head_dim; ++j) {
           uint32_t d, t = 0, n1 = 0, n2 = 0;
@@ -1207,10 +1227,18 @@ int cpu_attention(const char *who, const AttnCall &c, const AttnMode &m, int thr
     return set_error(KVECC_EINVAL, "cpu_paged_attention: heads not a multiple of kv heads");
   if (c.head_dim < 1) return set_error(KVECC_EINVAL, "cpu_paged_attention: empty head_dim");
   if (c.codec != KVECC_CODEC_NONE && c.codec != KVECC_CODEC_H74 && c.codec != KVECC_CODEC_H84 &&
-      c.codec != KVECC_CODEC_GOLAY && c.codec != KVECC_CODEC_GOLAY_PACKED)
+      c.codec != KVECC_CODEC_GOLAY && c.codec != KVECC_CODEC_GOLAY_PACKED && c.codec != KVECC_CODEC_INT4_PACKED)
     return set_error(KVECC_EINVAL,
-                     "cpu_paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed only)",
+                     "cpu_paged_attention: codec %d (int4, hamming74, hamming84, golay or golay_packed, or "
+                     "int4_packed, only)",
                      c.codec);
+  if (c.codec == KVECC_CODEC_INT4_PACKED) {  // as the device entries (kvecc.h)
+    if (windowed || std::strcmp(who, "cpu_paged_attention_window") == 0)
+      return set_error(KVECC_EINVAL, "%s: no windowed twin reads int4_packed caches", who);
+    if (c.head_dim % 8 != 0 || c.head_dim > 256)
+      return set_error(KVECC_EINVAL, "cpu_paged_attention: int4_packed head_dim %lld must be a multiple of 8 in [8, 256]",
+                       (long long)c.head_dim);
+  }
   if ((c.codec == KVECC_CODEC_NONE || c.codec == KVECC_CODEC_H74) && c.head_dim % 4 != 0)  // as the device entries
     return set_error(KVECC_EINVAL, "cpu_paged_attention: %s head_dim must be a multiple of 4",
                      c.codec == KVECC_CODEC_NONE ? "int4" : "hamming74");

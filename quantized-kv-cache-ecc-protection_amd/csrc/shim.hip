@@ -176,6 +176,25 @@ __global__ __launch_bounds__(kBlock) void shim_append_ragged_kernel(ShimAppendAr
 #include "shim_append_body.inc"
 #undef SHIM_APPEND_RAGGED
 }
+// Packed INT4 caches (KVECC_CODEC_INT4_PACKED, kvecc.h): the same body with the [packed] islands,
+// under names of their own -- the kernels above keep their text.  No codec and no bit count: there
+// is no code and nothing to inject.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void shim_append_packed_kernel(ShimAppendArgs a) {
+#define SHIM_APPEND_RAGGED 0
+#define SHIM_APPEND_PACKED 1
+#include "shim_append_body.inc"
+#undef SHIM_APPEND_PACKED
+#undef SHIM_APPEND_RAGGED
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void shim_append_packed_ragged_kernel(ShimAppendArgs a, const int32_t *q_spans) {
+#define SHIM_APPEND_RAGGED 1
+#define SHIM_APPEND_PACKED 1
+#include "shim_append_body.inc"
+#undef SHIM_APPEND_PACKED
+#undef SHIM_APPEND_RAGGED
+}
 
 struct ShimReadArgs {
   ShimGeom geo;
@@ -925,6 +944,13 @@ static void launch_append_nb(const ShimAppendArgs &a, const int32_t *q_spans, un
 
 template <typename T>
 static void launch_append(int codec, const ShimAppendArgs &a, const int32_t *q_spans, unsigned grid, hipStream_t st) {
+  if (codec == KVECC_CODEC_INT4_PACKED) {
+    if (q_spans)
+      KVECC_LAUNCH((shim_append_packed_ragged_kernel<T>), dim3(grid), dim3(kBlock), 0, st, a, q_spans);
+    else
+      KVECC_LAUNCH((shim_append_packed_kernel<T>), dim3(grid), dim3(kBlock), 0, st, a);
+    return;
+  }
   switch (codec) {
     case KVECC_CODEC_NONE: launch_append_nb<T, KVECC_CODEC_NONE>(a, q_spans, grid, st); break;
     case KVECC_CODEC_H74: launch_append_nb<T, KVECC_CODEC_H74>(a, q_spans, grid, st); break;
@@ -1138,8 +1164,14 @@ static int shim_append_impl(const void *k, const void *v, int64_t k_batch_stride
   if (batch == 0 || q_len == 0 || hkv == 0) return KVECC_OK;
   if (d < 1 || d > kMaxShimD)
     return set_error(KVECC_EINVAL, "shim_append: head_dim %lld not in [1, %d]", (long long)d, kMaxShimD);
-  if (codec < KVECC_CODEC_NONE || codec > KVECC_CODEC_GOLAY_PACKED)
+  if (codec < KVECC_CODEC_NONE || codec > KVECC_CODEC_INT4_PACKED)
     return set_error(KVECC_EINVAL, "shim_append: bad codec %d", codec);
+  if (codec == KVECC_CODEC_INT4_PACKED) {  // kvecc.h: whole dwords per row, no code to inject into
+    if (d % 8 != 0 || d > 256)
+      return set_error(KVECC_EINVAL, "shim_append: int4_packed head_dim %lld must be a multiple of 8 in [8, 256]",
+                       (long long)d);
+    if (inject) return set_error(KVECC_EINVAL, "shim_append: int4_packed has no code to inject errors into");
+  }
   const bool golay = codec == KVECC_CODEC_GOLAY || codec == KVECC_CODEC_GOLAY_PACKED;
   if (scale_rule != KVECC_SCALE_DIV7 && scale_rule != KVECC_SCALE_MUL_INV7)
     return set_error(KVECC_EINVAL, "shim_append: bad scale rule %d", scale_rule);

@@ -2,7 +2,13 @@
 // (SHIM_APPEND_RAGGED 1, with `q_spans`), included by shim.hip inside each kernel: the uniform
 // kernel's text is what it always was, so its code is too (a shared __device__ function changed it).
 // shim.hip defines SHIM_APPEND_RAGGED around each inclusion; it is no build switch.
+// The packed INT4 kernels (shim_append_packed_kernel, shim_append_packed_ragged_kernel,
+// KVECC_CODEC_INT4_PACKED) also define SHIM_APPEND_PACKED: the [packed] islands, in which a lane
+// owns the 8 adjacent values of one dword of the packed row; without it the preprocessed text is
+// what it was.
+#ifndef SHIM_APPEND_PACKED
   __shared__ uint8_t nib[kWavesPerBlock][kMaxShimD + 4];
+#endif
   const ShimGeom &geo = a.geo;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
   const uint32_t per_side = a.batch * a.qlen * geo.hkv;
@@ -21,10 +27,16 @@
     t = tq - (uint32_t)first;
     ri = ((uint32_t)base + t) * geo.hkv + h;
   }
+#ifdef SHIM_APPEND_PACKED  // [packed] no injection, so no seed
+  (void)ri;
+#else
   const uint32_t key0 = (a.seed0 + ri + (uint32_t)side) * a.rowmul;
+#endif
 #else
   const uint32_t b = bt / a.qlen, t = bt - b * a.qlen;
+#ifndef SHIM_APPEND_PACKED
   const uint32_t key0 = (a.seed0 + r + (uint32_t)side) * a.rowmul;
+#endif
   bool live = in_grid;
 #endif
   int64_t slot = 0;
@@ -40,6 +52,41 @@
     }
   }
 
+#ifdef SHIM_APPEND_PACKED  // [packed] lane i owns values 8i .. 8i + 7: dword i of the row of d / 2 bytes
+  // (d % 8 == 0 and d <= 256: the row's d / 8 dwords sit in the wave's first 32 lanes).  The
+  // row maximum, the scale and the quantiser are the byte kernels'; the lane's eight nibbles meet
+  // in its own register, nibble j at bits 4j -- byte i of the row holds value 2i low, 2i + 1
+  // high -- and leave as one dword store.  An input row that is 16-byte aligned (uniform per
+  // wave) is read with 16-byte loads, any other element by element.
+  constexpr int kPk = 8;
+  float v[kPk];
+  float amax = 0.0f;
+  const bool own = live && (uint32_t)(kPk * lane) < geo.d;
+  if (own) {
+#if SHIM_APPEND_RAGGED  // [spans] the input row is the token's place in the rectangle
+    const T *x = reinterpret_cast<const T *>(a.x[side]) + (int64_t)b * a.xb[side] + (int64_t)tq * a.xs[side] +
+                 (int64_t)h * a.xh[side];
+#else
+    const T *x = reinterpret_cast<const T *>(a.x[side]) + (int64_t)b * a.xb[side] + (int64_t)t * a.xs[side] +
+                 (int64_t)h * a.xh[side];
+#endif
+    if ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) {
+      constexpr int kVecs = kPk * (int)sizeof(T) / 16;  // 16-byte loads per lane: 2 (fp32) or 1
+      u32x4 raw[kVecs];
+#pragma unroll
+      for (int k = 0; k < kVecs; ++k) raw[k] = reinterpret_cast<const u32x4 *>(x + kPk * lane)[k];
+      T xe[kPk];
+      __builtin_memcpy(xe, raw, sizeof(xe));
+#pragma unroll
+      for (int j = 0; j < kPk; ++j) v[j] = to_f32<T>(xe[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPk; ++j) v[j] = to_f32<T>(x[kPk * lane + j]);
+    }
+#pragma unroll
+    for (int j = 0; j < kPk; ++j) amax = fmaxf(amax, fabsf(v[j]));
+  }
+#else
   constexpr int kPer = kMaxShimD / kWave;
   float v[kPer];
   float amax = 0.0f;
@@ -58,6 +105,7 @@
       amax = fmaxf(amax, fabsf(v[i]));
     }
   }
+#endif
 #pragma unroll
   for (int off = kWave / 2; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, kWave));
   const float scale = row_scale(amax, a.scale_rule);
@@ -68,6 +116,14 @@
     return recip ? nibble_of_quotient(div_recip(x, scale, inv)) : quantize_nibble(x, scale);
   };
 
+#ifdef SHIM_APPEND_PACKED  // [packed] eight nibbles, one dword, one store
+  if (!own) return;
+  uint32_t word = 0;
+#pragma unroll
+  for (int j = 0; j < kPk; ++j) word |= quant(v[j]) << (4 * j);
+  reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(a.cache[side]) + slot * KVECC_INT4_PACKED_ROW(geo.d))[lane] =
+      word;
+#else
   constexpr bool kGolay = CODEC == KVECC_CODEC_GOLAY || CODEC == KVECC_CODEC_GOLAY_PACKED;
   if (!kGolay) {
     if (!live) return;
@@ -107,3 +163,4 @@
       reinterpret_cast<int32_t *>(a.cache[side])[slot * geo.g + k] = (int32_t)cw;
     }
   }
+#endif

@@ -143,6 +143,7 @@ _RESTYPE = {
 F32, F16, BF16 = 0, 1, 2
 CODEC_NONE, CODEC_H74, CODEC_H84, CODEC_GOLAY = 0, 1, 2, 3
 CODEC_GOLAY_PACKED = 4  # shim caches only: 3-byte Golay codewords (kvecc.h)
+CODEC_INT4_PACKED = 5  # append-mode caches only: INT4, two nibbles per byte, rows of head_dim / 2 bytes (kvecc.h)
 # kvecc_mc_trial codecs (kvecc.h KVECC_MC_*)
 MC_CODECS = {"hamming74": 1, "hamming84": 2, "hamming84_interp": 3, "golay": 4}
 

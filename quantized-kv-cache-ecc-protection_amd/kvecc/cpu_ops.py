@@ -477,7 +477,8 @@ def fused_decode_dequantize_hamming84(codewords, scales, output_dtype=torch.floa
 # ============================================================================
 
 SHIM_CODECS = {"int4": _lib.CODEC_NONE, "hamming74": _lib.CODEC_H74, "hamming84": _lib.CODEC_H84,
-               "golay": _lib.CODEC_GOLAY, "golay_packed": _lib.CODEC_GOLAY_PACKED}
+               "golay": _lib.CODEC_GOLAY, "golay_packed": _lib.CODEC_GOLAY_PACKED,
+               "int4_packed": _lib.CODEC_INT4_PACKED}
 
 
 def shim_write(k, v, manager, layer, codec, n_bits, inject, ber, seed0, seq_id=0,
@@ -490,6 +491,8 @@ def shim_write(k, v, manager, layer, codec, n_bits, inject, ber, seed0, seq_id=0
 
 def shim_write_tensors(k, v, k_cache, v_cache, k_scales, v_scales, table, num_layers, block_size, hkv, d,
                        layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
+    from .ops import _refuse_int4_packed
+    _refuse_int4_packed(codec, "shim_write (overwrite mode)")
     batch, seq = k.shape[0], k.shape[1]
     if k.dtype not in _DT or v.dtype != k.dtype:
         raise TypeError(f"unsupported K/V dtype {k.dtype}/{v.dtype}")
@@ -505,11 +508,12 @@ def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table,
                         block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
     """Host twin of ops.shim_append_tensors (kvecc_cpu_shim_append): same
     arguments, placement, skip rules and seeds; K/V are made contiguous."""
-    from .ops import _check_shim_append_args, _head_rows  # pure torch, device-agnostic
+    from .ops import _check_append_inject, _check_shim_append_args, _head_rows  # pure torch, device-agnostic
     if k.device.type != "cpu":
         raise ValueError(f"the cpu backend writes host tensors, k is on {k.device}")
     batch, q_len = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
                                            num_layers, block_size, hkv, d, layer, codec)
+    _check_append_inject(codec, inject)
     k4 = _head_rows(k, batch, q_len, hkv, d).contiguous()
     v4 = _head_rows(v, batch, q_len, hkv, d).contiguous()
     _lib.call("kvecc_cpu_shim_append", _ptr(k4), _ptr(v4), _DT[k.dtype], batch, q_len, int(hkv), int(d),
@@ -524,11 +528,12 @@ def shim_append_ragged_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block
                                scale_rule=None):
     """Host twin of ops.shim_append_ragged_tensors (kvecc_cpu_shim_append_ragged):
     same arguments and rules; q_spans is a host tensor, K/V are made contiguous."""
-    from .ops import _check_q_spans, _check_shim_append_args, _head_rows
+    from .ops import _check_append_inject, _check_q_spans, _check_shim_append_args, _head_rows
     if k.device.type != "cpu":
         raise ValueError(f"the cpu backend writes host tensors, k is on {k.device}")
     batch, q_max = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
                                            num_layers, block_size, hkv, d, layer, codec)
+    _check_append_inject(codec, inject)
     _check_q_spans(q_spans, batch, k.device)
     k4 = _head_rows(k, batch, q_max, hkv, d).contiguous()
     v4 = _head_rows(v, batch, q_max, hkv, d).contiguous()
@@ -580,6 +585,8 @@ def shim_read(manager, layer, ctx, codec, interp, out_dtype, stats=None, seq_id=
 
 def shim_read_tensors(k_cache, v_cache, k_scales, v_scales, table, ctx, hkv, d, num_layers, block_size,
                       layer, codec, interp, out_dtype, stats=None):
+    from .ops import _refuse_int4_packed
+    _refuse_int4_packed(codec, "shim_read")
     shape = (hkv, ctx, d)
     k_out = torch.empty(shape, dtype=out_dtype)
     v_out = torch.empty(shape, dtype=out_dtype)
@@ -624,6 +631,8 @@ def paged_attention_into(query, k_cache, v_cache, block_table, context_lens, k_s
                                    max_context_len=max_context_len, interp=True)
         return out
     batch, heads, head_dim = query.shape
+    from .ops import _check_int4_packed_head_dim
+    _check_int4_packed_head_dim(codec, head_dim)
     num_blocks, num_layers, kv_heads, _ = k_cache.shape
     max_blocks = block_table.shape[1]
     _lib.call("kvecc_cpu_paged_attention", _ptr(query), _DT[query.dtype], _ptr(k_cache),
@@ -674,6 +683,8 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     from .ops import _check_interp_codec, _check_stats_codec, _check_window_args
     window, sinks = _check_window_args(window, sinks, query.shape[-1], interp, stats, repair)
     if window:  # kvecc_cpu_paged_attention_window
+        from .ops import _refuse_int4_packed
+        _refuse_int4_packed(codec, "windowed attention")
         return _call_chunk_entry("window", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, False, None,
                                  2, window=(window, sinks))

@@ -98,6 +98,13 @@ class ECCShimConfig:
     int32 per codeword) or "packed" (3-byte codewords, token rows padded to 4
     bytes: 132 instead of 172 B per row at head_dim 128).  "packed" needs the
     fused write / read.
+    ``int4_storage`` is the unprotected INT4 cache layout: "byte" (the default,
+    one nibble per byte, Hamming(8,4)'s layout) or "packed" (two nibbles per
+    byte, rows of head_dim / 2 bytes: kvecc.h KVECC_CODEC_INT4_PACKED).
+    "packed" needs codec="int4", cache_mode="append", fused=True,
+    kernel_attention=True, no attention_window and no error injection here,
+    and head_dim % 8 == 0, head_dim <= 256 and a pool under 4 GiB where the
+    caches are allocated; anything else raises ValueError naming the condition.
     ``cache_mode`` is "overwrite" (the reference's behaviour and the default:
     one cache for the whole batch, every forward writes from position 0) or
     "append": batch row b is sequence b with its own blocks, and every forward
@@ -208,7 +215,7 @@ class ECCShimConfig:
                  fused=True, scale_rule=None, golay_storage="int32", cache_mode="overwrite",
                  decode_stats=False, chunk_attention=False, interp_attention=False, kernel_attention=False,
                  stats_attention=False, counted_attention=False, repair_attention=False,
-                 attention_window=0, attention_sinks=0, evict_blocks=False):
+                 attention_window=0, attention_sinks=0, evict_blocks=False, int4_storage="byte"):
         if codec not in self.SUPPORTED_CODECS:
             raise ValueError(f"Unsupported codec: '{codec}'. "
                              f"Supported codecs: {sorted(self.SUPPORTED_CODECS)}")
@@ -275,6 +282,20 @@ class ECCShimConfig:
         self.attention_window = int(attention_window)
         self.attention_sinks = int(attention_sinks)
         self.evict_blocks = bool(evict_blocks)
+        if int4_storage not in ("byte", "packed"):
+            raise ValueError(f"int4_storage must be 'byte' or 'packed', not {int4_storage!r}")
+        if int4_storage == "packed":
+            # the packed layout is served by the append writers and the plain attention kernels only
+            for ok, what in ((codec == "int4", f"codec='int4', not {codec!r}"),
+                             (cache_mode == "append", f"cache_mode='append', not {cache_mode!r}"),
+                             (bool(fused), "fused=True"),
+                             (bool(kernel_attention), "kernel_attention=True (no read + SDPA path unpacks it)"),
+                             (not attention_window, "attention_window=0 (no windowed kernel reads it)"),
+                             (not decode_stats, "decode_stats=False (the counting read does not unpack it)"),
+                             (not (inject_errors and ber > 0), "no error injection (there is no code to inject into)")):
+                if not ok:
+                    raise ValueError(f"int4_storage='packed' needs {what}")
+        self.int4_storage = int4_storage
 
 
 class SimpleBlockManager:
@@ -293,7 +314,7 @@ class SimpleBlockManager:
     """
 
     def __init__(self, num_blocks, block_size, num_layers, num_kv_heads, head_dim, device="cuda",
-                 codec="hamming84", golay_storage="int32"):
+                 codec="hamming84", golay_storage="int32", int4_storage="byte"):
         self.num_blocks = num_blocks
         self.block_size = block_size
         self.num_layers = num_layers
@@ -305,7 +326,21 @@ class SimpleBlockManager:
         self.golay_packed = codec == "golay" and golay_storage == "packed"
         # the codec name the fused shim kernels take (ops.SHIM_CODECS)
         self.shim_codec = "golay_packed" if self.golay_packed else codec
-        if self.golay_packed:
+        self.int4_packed = int4_storage == "packed"
+        if self.int4_packed:  # two nibbles per byte (kvecc.h KVECC_CODEC_INT4_PACKED)
+            if codec != "int4":
+                raise ValueError(f"int4_storage='packed' needs codec='int4', not {codec!r}")
+            if head_dim % 8 or not 8 <= head_dim <= 256:
+                raise ValueError(f"int4_storage='packed' needs head_dim a multiple of 8 in [8, 256], not {head_dim}")
+            if not self.fits_buffer_kernels(num_blocks, num_layers, num_kv_heads, block_size, head_dim, codec,
+                                            golay_storage, int4_storage):
+                raise ValueError("int4_storage='packed' needs a pool under 4 GiB per cache (fits_buffer_kernels): "
+                                 "its kernels address the caches through buffer descriptors only")
+            self.shim_codec = "int4_packed"
+        if self.int4_packed:
+            self.values_per_head = block_size * head_dim // 2
+            self.cache_dtype = torch.uint8
+        elif self.golay_packed:
             self.values_per_head = block_size * golay_packed_row_bytes((head_dim + 2) // 3)
             self.cache_dtype = torch.uint8
         elif codec == "golay":
@@ -325,7 +360,7 @@ class SimpleBlockManager:
         # whether the paged attention kernels address these caches through buffer descriptors
         # (the interpolating, counted and repairing kernels exist in that form only)
         self.buffer_addressable = self.fits_buffer_kernels(
-            num_blocks, num_layers, num_kv_heads, block_size, head_dim, codec, golay_storage)
+            num_blocks, num_layers, num_kv_heads, block_size, head_dim, codec, golay_storage, int4_storage)
         self.free_blocks = list(range(num_blocks))
         self.seq_to_blocks = {}
         self.seq_to_len = {}
@@ -347,7 +382,7 @@ class SimpleBlockManager:
 
     @staticmethod
     def fits_buffer_kernels(num_blocks, num_layers, num_kv_heads, block_size, head_dim, codec="hamming84",
-                            golay_storage="int32"):
+                            golay_storage="int32", int4_storage="byte"):
         """True iff a cache of this shape and storage is under the 4 GiB switch of
         the paged attention entries (csrc/attention.hip, attn_setup's `fits`): one
         cache's bytes and one scale array's bytes (4 per token row) both fit 32 bits.
@@ -358,6 +393,8 @@ class SimpleBlockManager:
         if codec == "golay":
             g = (head_dim + 2) // 3
             row_bytes = golay_packed_row_bytes(g) if golay_storage == "packed" else 4 * g
+        elif codec == "int4" and int4_storage == "packed":  # two values per byte
+            row_bytes = head_dim // 2
         else:  # one byte per value (int4, hamming74, hamming84)
             row_bytes = head_dim
         return rows * row_bytes <= 0xFFFFFFFF and rows * 4 <= 0xFFFFFFFF
@@ -1365,7 +1402,8 @@ def patch_model_with_ecc_attention(model, config, num_blocks=256):
                                  num_layers=len(layers), num_kv_heads=num_kv_heads,
                                  head_dim=head_dim, device=next(model.parameters()).device,
                                  codec=config.codec,
-                                 golay_storage=getattr(config, "golay_storage", "int32"))
+                                 golay_storage=getattr(config, "golay_storage", "int32"),
+                                 int4_storage=getattr(config, "int4_storage", "byte"))
     backend = ECCBackend(manager, config, num_heads)
     rotary = None if model_type == "gpt2" else _find_rotary_embedding(model, layers)
     originals = {}

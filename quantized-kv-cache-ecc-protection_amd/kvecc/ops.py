@@ -658,7 +658,23 @@ def fused_decode_dequantize_hamming84(codewords, scales, output_dtype=torch.floa
 # ============================================================================
 
 SHIM_CODECS = {"int4": _lib.CODEC_NONE, "hamming74": _lib.CODEC_H74, "hamming84": _lib.CODEC_H84,
-               "golay": _lib.CODEC_GOLAY, "golay_packed": _lib.CODEC_GOLAY_PACKED}
+               "golay": _lib.CODEC_GOLAY, "golay_packed": _lib.CODEC_GOLAY_PACKED,
+               "int4_packed": _lib.CODEC_INT4_PACKED}
+# "int4_packed" (kvecc.h KVECC_CODEC_INT4_PACKED): int4's nibbles two per byte, rows of head_dim / 2
+# bytes -- an append-mode layout served by shim_append*_tensors and the plain paged-attention entries
+INT4_PACKED = "int4_packed"
+
+
+def _refuse_int4_packed(codec, what):
+    """The entries outside the append writers and plain attention refuse the packed layout."""
+    if codec == INT4_PACKED:
+        raise ValueError(f"{what} does not serve codec 'int4_packed' (append-mode caches and plain paged "
+                         "attention only)")
+
+
+def _check_int4_packed_head_dim(codec, head_dim):
+    if codec == INT4_PACKED and (head_dim % 8 or not 8 <= head_dim <= 256):
+        raise ValueError(f"int4_packed head_dim {head_dim} must be a multiple of 8 in [8, 256]")
 
 
 def shim_write(k, v, manager, layer, codec, n_bits, inject, ber, seed0, seq_id=0,
@@ -677,6 +693,7 @@ def shim_write_tensors(k, v, k_cache, v_cache, k_scales, v_scales, table, num_la
                        layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
     """shim_write on the cache tensors themselves (the torch.ops.kvecc.shim_write
     kernel): table = the sequence's block-table row, int32 [max_blocks]."""
+    _refuse_int4_packed(codec, "shim_write (overwrite mode)")
     batch, seq = k.shape[0], k.shape[1]
     if k.dtype not in _DT or v.dtype != k.dtype:
         raise TypeError(f"unsupported K/V dtype {k.dtype}/{v.dtype}")
@@ -713,6 +730,7 @@ def shim_read(manager, layer, ctx, codec, interp, out_dtype, stats=None, seq_id=
 def shim_read_tensors(k_cache, v_cache, k_scales, v_scales, table, ctx, hkv, d, num_layers, block_size,
                       layer, codec, interp, out_dtype, stats=None):
     """shim_read on the cache tensors themselves (the torch.ops.kvecc.shim_read kernel)."""
+    _refuse_int4_packed(codec, "shim_read")
     dev = k_cache.device
     shape = (hkv, ctx, d)
     k_out = torch.empty(shape, dtype=out_dtype, device=dev)
@@ -724,7 +742,7 @@ def shim_read_tensors(k_cache, v_cache, k_scales, v_scales, table, ctx, hkv, d, 
 
 
 _SHIM_CACHE_DT = {"int4": torch.uint8, "hamming74": torch.uint8, "hamming84": torch.uint8,
-                  "golay": torch.int32, "golay_packed": torch.uint8}
+                  "golay": torch.int32, "golay_packed": torch.uint8, "int4_packed": torch.uint8}
 
 
 def _check_shim_read_args(k_cache, v_cache, k_scales, v_scales, block_table, ctx, head_dim, layer, codec,
@@ -737,6 +755,7 @@ def _check_shim_read_args(k_cache, v_cache, k_scales, v_scales, block_table, ctx
     Returns (batch, layers, hkv, block_size)."""
     if codec not in _SHIM_CACHE_DT:
         raise ValueError(f"shim codec {codec!r} (int4, hamming74, hamming84, golay or golay_packed)")
+    _refuse_int4_packed(codec, "shim_read")
     if out_dtype not in _DT:
         raise ValueError(f"out_dtype must be fp32/fp16/bf16, got {out_dtype}")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
@@ -789,7 +808,9 @@ def _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_ta
     contiguous, start_pos int32 [batch], one device for every tensor.  A
     mismatch raises ValueError.  Returns (batch, q_len)."""
     if codec not in _SHIM_CACHE_DT:
-        raise ValueError(f"shim codec {codec!r} (int4, hamming74, hamming84, golay or golay_packed)")
+        raise ValueError(f"shim codec {codec!r} (int4, hamming74, hamming84, golay or golay_packed, or "
+                         "int4_packed)")
+    _check_int4_packed_head_dim(codec, d)
     if k.dtype not in _DT or v.dtype != k.dtype:
         raise ValueError(f"K/V must share one of fp32/fp16/bf16, got {k.dtype}/{v.dtype}")
     if k.dim() < 3 or k.shape != v.shape:
@@ -803,7 +824,8 @@ def _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_ta
     for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
         if c.dtype != _SHIM_CACHE_DT[codec]:
             raise ValueError(f"{codec} {name} must be {_SHIM_CACHE_DT[codec]}, got {c.dtype}")
-    per = {"golay": (d + 2) // 3, "golay_packed": (3 * ((d + 2) // 3) + 3) // 4 * 4}.get(codec, d)
+    per = {"golay": (d + 2) // 3, "golay_packed": (3 * ((d + 2) // 3) + 3) // 4 * 4,
+           "int4_packed": d // 2}.get(codec, d)
     if tuple(k_cache.shape[1:]) != (num_layers, hkv, block_size * per) or block_size < 1:
         raise ValueError(f"{codec} caches must be [blocks, {num_layers}, {hkv}, {block_size}*{per}], got "
                          f"{tuple(k_cache.shape)}")
@@ -827,6 +849,12 @@ def _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_ta
     return batch, q_len
 
 
+def _check_append_inject(codec, inject):
+    """A packed INT4 cache holds no code: there is nothing to inject errors into."""
+    if codec == INT4_PACKED and inject:
+        raise ValueError("int4_packed has no code to inject errors into: inject must be off")
+
+
 def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos, num_layers,
                         block_size, hkv, d, layer, codec, n_bits, inject, ber, seed0, scale_rule=None):
     """Append-mode cache write (kvecc_shim_append): K, V [batch, q_len, hkv*d] or
@@ -839,6 +867,7 @@ def shim_append_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block_table,
         raise ValueError(f"the hip backend writes GPU tensors, k is on {k.device}")
     batch, q_len = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
                                            num_layers, block_size, hkv, d, layer, codec)
+    _check_append_inject(codec, inject)
     k4 = _head_rows(k, batch, q_len, hkv, d)
     v4 = _head_rows(v, batch, q_len, hkv, d)
     _lib.call("kvecc_shim_append", _ptr(k4), _ptr(v4), k4.stride(0), k4.stride(1), k4.stride(2),
@@ -914,6 +943,7 @@ def shim_append_ragged_tensors(k, v, k_cache, v_cache, k_scales, v_scales, block
     batch, q_max = _check_shim_append_args(k, v, k_cache, v_cache, k_scales, v_scales, block_table, start_pos,
                                            num_layers, block_size, hkv, d, layer, codec)
     _check_q_spans(q_spans, batch, k.device)
+    _check_append_inject(codec, inject)
     k4 = _head_rows(k, batch, q_max, hkv, d)
     v4 = _head_rows(v, batch, q_max, hkv, d)
     _lib.call("kvecc_shim_append_ragged", _ptr(k4), _ptr(v4), k4.stride(0), k4.stride(1), k4.stride(2),
@@ -1079,10 +1109,12 @@ def check_scrub_stats(stats, device):
 # (int4 and hamming74: Hamming(8,4)'s layout, one value per byte -- kvecc.h "byte caches")
 _ATTN_ROW_WORDS = {"int4": lambda d: d, "hamming74": lambda d: d,
                    "hamming84": lambda d: d, "golay": lambda d: (d + 2) // 3,
-                   "golay_packed": lambda d: (3 * ((d + 2) // 3) + 3) // 4 * 4}  # KVECC_GOLAY_PACKED_ROW
+                   "golay_packed": lambda d: (3 * ((d + 2) // 3) + 3) // 4 * 4,  # KVECC_GOLAY_PACKED_ROW
+                   "int4_packed": lambda d: d // 2}  # KVECC_INT4_PACKED_ROW
 _ATTN_CACHE_DT = {"int4": torch.uint8, "hamming74": torch.uint8,
-                  "hamming84": torch.uint8, "golay": torch.int32, "golay_packed": torch.uint8}
-_ATTN_CODEC_NAMES = "int4, hamming74, hamming84, golay or golay_packed"
+                  "hamming84": torch.uint8, "golay": torch.int32, "golay_packed": torch.uint8,
+                  "int4_packed": torch.uint8}
+_ATTN_CODEC_NAMES = "int4, hamming74, hamming84, golay or golay_packed, or int4_packed"
 _attn_ws = {}  # (device index, stream) -> float32 workspace, grown on demand
 _attn_ws_retired = []  # outgrown workspaces stay alive: a captured HIP graph may still name them
 
@@ -1111,6 +1143,7 @@ def _check_attn_caches(heads, head_dim, k_cache, v_cache, block_size, codec):
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
         raise ValueError("k_cache / v_cache must share one [blocks, layers, kv_heads, row] shape")
     kvh, row = k_cache.shape[2:]
+    _check_int4_packed_head_dim(codec, head_dim)
     per = _ATTN_ROW_WORDS[codec](head_dim)
     for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
         if c.dtype != _ATTN_CACHE_DT[codec]:
@@ -1344,6 +1377,7 @@ def paged_attention_chunk_into(query, k_cache, v_cache, block_table, context_len
     without q_spans, q_len 1 included.  window=0: no window, sinks ignored."""
     window, sinks = _check_window_args(window, sinks, query.shape[-1], interp, stats, repair)
     if window:
+        _refuse_int4_packed(codec, "windowed attention")
         return _call_chunk_entry("window", query, k_cache, v_cache, block_table, context_lens, k_scales, v_scales,
                                  out, layer_idx, block_size, sm_scale, codec, max_context_len, q_spans, False, None,
                                  window=(window, sinks))

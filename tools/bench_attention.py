@@ -32,6 +32,8 @@ hamming74 and hamming84 on clean encoded caches of the same nibbles, hamming74 a
 injected at BER 1e-3, and shim_read_batch + repeat_interleave + masked SDPA over the int4 and
 hamming74 caches, the path ECCShimConfig(kernel_attention=True) replaces.
 
+--packed times the packed INT4 kernels (codec int4_packed) beside int4 and hamming84 over the same values
+(bench_packed).
 --stats --codec golay | golay_packed times the Golay counted entry (kvecc_paged_attention_golay_stats)
 against the uncounted Golay kernels and the counting read + masked SDPA (bench_golay_stats).
 --stats times the counted entry (kvecc_paged_attention_stats, Hamming(8,4)) in one process at
@@ -112,6 +114,9 @@ def main():
     ap.add_argument("--interp", action="store_true", help="the interpolating entry against (a), (b), (c) above")
     ap.add_argument("--bytes", action="store_true",
                     help="the byte family (int4, hamming74) beside hamming84, alternated in one process")
+    ap.add_argument("--packed", action="store_true",
+                    help="packed INT4 (int4_packed, two nibbles per byte) beside int4 and hamming84 over the same "
+                         "values, alternated in one process")
     ap.add_argument("--stats", action="store_true",
                     help="the counted entry beside the uncounted kernels and the counting read + SDPA")
     ap.add_argument("--repair", action="store_true",
@@ -128,6 +133,8 @@ def main():
         return bench_interp(args, ops, dev)
     if args.bytes:
         return bench_bytes(args, ops, dev)
+    if args.packed:
+        return bench_packed(args, ops, dev)
     if args.repair:
         return bench_repair(args, ops, dev)
     if args.window:
@@ -466,6 +473,78 @@ def bench_bytes(args, ops, dev):
             print(json.dumps({"kernel": "paged_attention_bytes", "batch": args.batch, "q_len": n,
                               "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
                               "block_size": args.bs, **res}), flush=True)
+        del caches, x
+
+
+def bench_packed(args, ops, dev):
+    """--packed: the packed INT4 kernels (codec int4_packed: rows of d / 2 bytes) beside the byte INT4 and the
+    Hamming(8,4) kernels over the same values and scales, MHA and 4-way GQA, a decode step and a 16-token
+    chunk: every case warmed up, then --passes rounds that visit the cases in turn.  One JSON line per
+    (kv_heads, q_len) with the medians, the spreads, the K/V bytes a call reads and the largest difference
+    between the packed and the byte INT4 outputs."""
+    import statistics
+    import time
+
+    from kvecc.memory_layout import kv_cache_pair
+    g = torch.Generator(device=dev).manual_seed(0)
+    nb = (args.ctx + args.bs - 1) // args.bs
+    blocks = args.batch * nb
+    sm = 1 / math.sqrt(args.d)
+    for kvh in (args.kv_heads, max(1, args.heads // 4)):
+        x = torch.randint(0, 16, (2, blocks, 1, kvh, args.bs * args.d), device=dev, generator=g, dtype=torch.uint8)
+        caches = {}
+        for codec in ("int4_packed", "int4", "hamming84"):
+            row = args.bs * args.d // (2 if codec == "int4_packed" else 1)
+            kc, vc = kv_cache_pair((blocks, 1, kvh, row), torch.uint8, dev)
+            for side, dst in enumerate((kc, vc)):
+                if codec == "int4_packed":
+                    dst.copy_(x[side][..., 0::2] | x[side][..., 1::2] << 4)
+                else:
+                    dst.view(-1).copy_(byte_encode(ops, codec, x[side].reshape(-1)))
+            caches[codec] = (kc, vc)
+        ks = torch.rand(blocks, 1, kvh, args.bs, device=dev, generator=g)
+        vs = torch.rand_like(ks)
+        table = torch.randperm(blocks, device=dev, generator=g).to(torch.int32).view(args.batch, nb)
+        lens = torch.full((args.batch,), args.ctx, dtype=torch.int32, device=dev)
+        for n in (1, 16):
+            qt = torch.randn(args.batch, args.heads, n, args.d, device=dev, generator=g).half().transpose(1, 2)
+            q1 = qt[:, 0].contiguous()
+            outs = {c: torch.empty(q1.shape if n == 1 else qt.shape, dtype=qt.dtype, device=dev) for c in caches}
+
+            def attend(codec):
+                kc, vc = caches[codec]
+                if n == 1:
+                    return lambda: ops.paged_attention_into(q1, kc, vc, table, lens, ks, vs, outs[codec], 0, args.bs,
+                                                            sm, codec, args.ctx)
+                return lambda: ops.paged_attention_chunk_into(qt, kc, vc, table, lens, ks, vs, outs[codec], 0,
+                                                              args.bs, sm, codec, args.ctx)
+
+            cases = {c: attend(c) for c in caches}
+            for fn in cases.values():
+                t0 = time.perf_counter()
+                while True:
+                    for _ in range(args.warmup):
+                        fn()
+                    torch.cuda.synchronize()
+                    if time.perf_counter() - t0 >= args.warmup_s:
+                        break
+            passes = {c: [] for c in cases}
+            for _ in range(args.passes):
+                for c, fn in cases.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.iters):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    passes[c].append(e0.elapsed_time(e1) / args.iters * 1e3)
+            res = {c: {"us_per_call": round(statistics.median(p), 2), "pass_us": [round(v, 2) for v in p],
+                       "spread_us": round(max(p) - min(p), 2),
+                       "kv_bytes_per_call": 2 * caches[c][0].numel() + 8 * ks.numel()} for c, p in passes.items()}
+            diff = (outs["int4_packed"].float() - outs["int4"].float()).abs().max().item()
+            print(json.dumps({"kernel": "paged_attention_packed", "batch": args.batch, "q_len": n,
+                              "heads": args.heads, "kv_heads": kvh, "head_dim": args.d, "ctx": args.ctx,
+                              "block_size": args.bs, **res, "packed_vs_int4_max_abs_diff": diff}), flush=True)
         del caches, x
 
 
